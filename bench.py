@@ -14,7 +14,12 @@ solve every robot's QP, plus -- on N > 1 -- the end-of-step RCCL all-gather of
 u0 (the only exchange the path has).  Inputs are resident in HBM before the
 timed region.
 
-Prints ONE JSON line on rank 0 (metric/value/unit/... + roofline + cpu_baseline).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and
+prints the headline (metric / value / unit / ms_per_step / ...).  --full adds everything
+else the benchmark measures, each outside `value`: the roofline figures, iteration and
+status statistics, the CPU baseline, the device callers, the no_hint and two_streams
+sub-lines (config 1: the cold-start loop and the CPU baseline).  --dump-outputs DIR
+writes what the last timed step returned to its caller as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -41,6 +46,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="config2", choices=sorted(CONFIGS) + ["config1"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline, iteration / status "
+                         "statistics, CPU baseline, device callers, no_hint and two_streams sub-lines (config1: "
+                         "the cold loop and the CPU baseline); the --no-* switches below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller "
+                         "(u0, status, iterations; config1: the tick's forces) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--warm-fleet", action="store_true",
                     help="a fleet solved tick after tick: the batches are a drift sequence (x0 + N(0, 2e-3) "
                          "per tick, visited 0 1 2 3 2 1 ...) and the engine remembers each robot's active set "
@@ -135,6 +147,18 @@ def _host_cores():
         avail = os.cpu_count() or 1
     # the box's share: OMP_NUM_THREADS / MAX_JOBS are set to it (16 for one GPU)
     return max(1, min(avail, int(os.environ.get("OMP_NUM_THREADS", "16")), 16))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: DIR/<name>.npy per returned array; integer arrays (status, iteration
+    counts) are stored as float32 (exact at their sizes), float arrays keep f32 / f64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def time_callers(eng, h, B, N, dev, stream, reps=20):
@@ -255,7 +279,7 @@ def rehearse_cpu(args, world, rank, dist):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     if rank == 0:
         el = float(tmax.item())
-        cpu = None if args.no_cpu else cpu_baseline_line(h, N, args.cpu_seconds, world)
+        cpu = cpu_baseline_line(h, N, args.cpu_seconds, world) if args.full and not args.no_cpu else None
         print(json.dumps({"metric": "QP solves/sec (whole node), horizon=10 GRF QP, at 1/2/4/8 MI355X",
                           "value": world * Bpg * args.steps / el, "unit": "QP/s",
                           "n_gpus": world, "steps": args.steps, "warmup": 0,
@@ -333,7 +357,10 @@ def bench_config1(args):
         active set, interior-point class only) disabled, every tick solved cold."""
         ctl = mpc.ModelPredictiveController(LinearMpcConfig, AliengoConfig)
         mpc_ms, other_ms, states, iters = [], [], [], []
+        t_timed = time.perf_counter()
         for it in range(n_iter):
+            if it == args.warmup * 20:   # a timed step: one MPC tick and the 19 iterations after it
+                t_timed = time.perf_counter()
             rd = _SyntheticRobotData(it * 1e-3)
             table = gait_table(args.gait, (it // 20) % 10, N).reshape(-1)
             if it == 0 and not warm:
@@ -351,11 +378,28 @@ def bench_config1(args):
                                        [np.asarray(f) for f in rd.pos_base_feet]))
                 else:
                     other_ms.append(dt)
+        step_ms = (time.perf_counter() - t_timed) * 1e3 / max(args.steps, 1)
         assert np.all(np.isfinite(u))
-        return mpc_ms, other_ms, states, iters
+        return mpc_ms, other_ms, states, iters, step_ms, u
 
-    mpc_ms, other_ms, states, iters = run(True)
-    cold_ms, _, _, cold_iters = run(False)
+    mpc_ms, other_ms, states, iters, step_ms, u_last = run(True)
+    if args.dump_outputs:   # the forces the last timed MPC tick returned (held until the next tick)
+        dump_outputs(args.dump_outputs, {"u": np.asarray(u_last, np.float64)})
+    med = float(np.median(mpc_ms))
+    head = {
+        "metric": f"drop-in MPC tick latency (B=1, Aliengo, horizon 16, {args.gait})",
+        "value": med, "unit": "ms", "n_gpus": 1, "steps": len(mpc_ms), "warmup": args.warmup,
+        "ms_per_step": step_ms,
+        "higher_is_better": False, "dtype": "f64", "data": "synthetic Aliengo trot states (no simulator)",
+        "config": {"workload": "config1: ModelPredictiveController drop-in, scripts/mujoco_aliengo.py loop, "
+                               f"LinearMpcConfig.horizon = 16, gait {args.gait}", "batch": 1, "horizon": N,
+                   "gait": args.gait},
+        "mpc_tick_ms": {"median": med, "p90": float(np.percentile(mpc_ms, 90)), "mean": float(np.mean(mpc_ms))},
+    }
+    if not args.full:
+        print(json.dumps(head))
+        return
+    cold_ms, _, _, cold_iters, _, _ = run(False)
     cpu = None
     if not args.no_cpu:
         from mpcqp.params import pack_robot, ROBOT_PRESETS
@@ -370,15 +414,8 @@ def bench_config1(args):
                "sample": f"{done} MPC ticks of the same run's states, 1 thread ({_cpu_model()}): compiled "
                          "restatement of the reference's formulation + float64 Goldfarb-Idnani QP "
                          "(oracle/cpu_mpc.cpp)"}
-    med = float(np.median(mpc_ms))
     print(json.dumps({
-        "metric": f"drop-in MPC tick latency (B=1, Aliengo, horizon 16, {args.gait})",
-        "value": med, "unit": "ms", "n_gpus": 1, "steps": len(mpc_ms), "warmup": args.warmup,
-        "higher_is_better": False, "dtype": "f64", "data": "synthetic Aliengo trot states (no simulator)",
-        "config": {"workload": "config1: ModelPredictiveController drop-in, scripts/mujoco_aliengo.py loop, "
-                               f"LinearMpcConfig.horizon = 16, gait {args.gait}", "batch": 1, "horizon": N,
-                   "gait": args.gait},
-        "mpc_tick_ms": {"median": med, "p90": float(np.percentile(mpc_ms, 90)), "mean": float(np.mean(mpc_ms))},
+        **head,
         "warm_start": "the drop-in's default: each tick's interior-point solve (n > 128) starts from the "
                       "previous tick's verified active set (mpcqp_set_warm_start); the dense classes "
                       "always start cold",
@@ -478,6 +515,7 @@ def main():
     iters = [torch.empty((Bpg,), dtype=torch.int32, device=dev) for _ in range(nbat)]
     stream = torch.cuda.current_stream(dev)
     gather_events = []
+    gathered = [None]   # N > 1: the last step's all-gathered u0 (what the caller receives)
 
     def step(k, ev=None):
         d = dev_b[bi(k)]
@@ -491,11 +529,11 @@ def main():
             if ev is not None:   # the RCCL all-gather, timed on its own
                 g = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 g[0].record(stream)
-                gather_u0(u0)
+                gathered[0] = gather_u0(u0)
                 g[1].record(stream)
                 gather_events.append(g)
             else:
-                gather_u0(u0)
+                gathered[0] = gather_u0(u0)
 
     for k in range(args.warmup):
         step(k)
@@ -536,6 +574,54 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    kavg_s = sum(kern_ms) / len(kern_ms) / 1e3
+    qps = world * Bpg * args.steps / elapsed
+
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        kl = bi(args.steps - 1)   # the last timed step's batch
+        out = {"u0": u0.cpu().numpy(), "status": status[kl].cpu().numpy(), "iterations": iters[kl].cpu().numpy()}
+        if gathered[0] is not None:
+            out["u0_gathered"] = gathered[0].cpu().numpy()
+        dump_outputs(args.dump_outputs, out)
+
+    gather_label = ""
+    if world > 1 and not args.no_gather:
+        be = dist.get_backend()
+        gather_label = " + " + ("RCCL" if be == "nccl" else be) + " all-gather of u0"
+    workload = (f"{args.config}: batch {Bpg}/GPU, horizon {N}, gaits {'+'.join(gaits)}, "
+                f"robots {'+'.join(robots)}" + (f", cone tilt <= {tilt} deg" if tilt else ""))
+    data = "synthetic (seeded SURVEY §8(d) states, gait tables, feet; seed = base + rank)"
+    if args.standing_every:
+        workload += f", every {args.standing_every}th robot standing"
+    if args.cross_leg_r:
+        workload += ", R coupling every pair of legs (the interior-point class's 12 x 12 stage weights)"
+    if args.warm_fleet:
+        workload += (", warm fleet: consecutive ticks of one fleet (x0 drifting "
+                     "N(0, 2e-3) per tick), each robot's active set remembered")
+        data += "; warm start (mpcqp_set_warm_start): not comparable with the cold lines"
+    head = {
+        "metric": "QP solves/sec (whole node), horizon=10 GRF QP, at 1/2/4/8 MI355X",
+        "value": qps,
+        "unit": "QP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": data,
+        "config": {"workload": workload,
+                   "batch_per_gpu": Bpg, "horizon": N, "global_batch": world * Bpg,
+                   "parallelism": f"robot-sharded x{world}" + gather_label},
+    }
+    if not args.full:   # the plain run: the headline and the timed loop's own event time
+        if rank == 0:
+            print(json.dumps({**head, "kernel_ms_avg": kavg_s * 1e3}))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # algorithmic work per launch: per-robot n_eff and executed iterations
     flops_launch = []
@@ -557,11 +643,9 @@ def main():
     steps_per_bat = [sum(1 for s in range(args.steps) if bi(s) == k) for k in range(nbat)]
     F_avg = sum(f * c for f, c in zip(flops_launch, steps_per_bat)) / args.steps
     E_avg = sum(f * c for f, c in zip(exec_launch, steps_per_bat)) / args.steps
-    kavg_s = sum(kern_ms) / len(kern_ms) / 1e3
     achieved = F_avg / kavg_s / 1e12
     it_all = np.concatenate(it_all)
 
-    qps = world * Bpg * args.steps / elapsed
     # HBM traffic cannot be counted inside this process (PMC needs a rocprofv3 pass of its
     # own): it is attached only from a profile of THIS build (library SHA-256 match) of
     # the same config and batch, with its provenance; otherwise null
@@ -644,29 +728,10 @@ def main():
     gather_ms = (sum(a.elapsed_time(b) for a, b in gather_events) / len(gather_events)
                  if gather_events else None)
 
-    gather_label = ""
-    if world > 1 and not args.no_gather:
-        be = dist.get_backend()
-        gather_label = " + " + ("RCCL" if be == "nccl" else be) + " all-gather of u0"
     if rank == 0:
         cpu = None if args.no_cpu else cpu_baseline_line(host[0], N, args.cpu_seconds, world)
         line = {
-            "metric": "QP solves/sec (whole node), horizon=10 GRF QP, at 1/2/4/8 MI355X",
-            "value": qps,
-            "unit": "QP/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (seeded SURVEY §8(d) states, gait tables, feet; seed = base + rank)",
-            "config": {"workload": f"{args.config}: batch {Bpg}/GPU, horizon {N}, gaits {'+'.join(gaits)}, "
-                                   f"robots {'+'.join(robots)}" + (f", cone tilt <= {tilt} deg" if tilt else ""),
-                       "batch_per_gpu": Bpg, "horizon": N, "global_batch": world * Bpg,
-                       "parallelism": f"robot-sharded x{world}" + gather_label},
+            **head,
             # the governing pipe is the FP64 vector ALU (VALU): no MFMA instruction is on
             # the path (gfx950's FP64 MFMA peak equals its FP64 VALU peak)
             "roofline": {"bound": "valu", "pipe": "fp64 VALU", "achieved": achieved, "peak": PEAK_FP64_TFLOPS,
@@ -704,14 +769,6 @@ def main():
             line["two_streams"] = two_streams
         if gather_ms is not None:
             line["gather_ms_avg"] = gather_ms
-        if args.standing_every:
-            line["config"]["workload"] += f", every {args.standing_every}th robot standing"
-        if args.cross_leg_r:
-            line["config"]["workload"] += ", R coupling every pair of legs (the interior-point class's 12 x 12 stage weights)"
-        if args.warm_fleet:
-            line["config"]["workload"] += (", warm fleet: consecutive ticks of one fleet (x0 drifting "
-                                           "N(0, 2e-3) per tick), each robot's active set remembered")
-            line["data"] += "; warm start (mpcqp_set_warm_start): not comparable with the cold lines"
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

@@ -92,7 +92,7 @@ def test_bench_rehearsal_world8(config, total):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["OMP_NUM_THREADS"] = "1"
     # the CPU baseline leg runs once (config 2's 1 024-robot shard); the big shards skip it
-    cpu = ["--cpu-seconds", "0.4"] if config == "config2" else ["--no-cpu"]
+    cpu = ["--full", "--cpu-seconds", "0.4"] if config == "config2" else ["--no-cpu"]
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--rehearse-cpu",
            "--config", config, "--steps", "2"] + (["--total", str(total)] if total else []) + cpu
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, check=True)

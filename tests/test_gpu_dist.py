@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                           "--cpu-seconds", "0.5"], capture_output=True, text=True, timeout=600, check=True)
     line = json.loads(out.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
@@ -27,9 +27,42 @@ def test_bench_contract_line():
     assert line["status_ok_frac"] == 1.0
 
 
+def test_bench_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """Without --full the line is the headline only (no roofline / CPU baseline / sub-lines),
+    and --dump-outputs writes what the last timed step returned: step 2 of 3 solves the seeded
+    batch 2 (seed 3000), so u0 must match an in-process solve of that batch.  Both are the same
+    float64 kernel on the same inputs; 1e-5 relative is a tenth of the engine's 1e-4 contract."""
+    import numpy as np
+    import torch
+    from mpcqp import LinearMpc
+    from mpcqp.synthetic import make_batch
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, check=True)
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(1024 * 1e3 / line["ms_per_step"], rel=1e-9)
+    for k in ("roofline", "cpu_baseline", "callers", "no_hint", "two_streams", "status_ok_frac"):
+        assert k not in line, k
+    got = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in ("u0", "status", "iterations")}
+    assert got["u0"].shape == (1024, 12) and got["u0"].dtype == np.float32
+    assert got["status"].shape == (1024,) and (got["status"] == 0).all()
+    assert (got["iterations"] >= 0).all() and got["iterations"].dtype == np.float32
+    bt = make_batch(1024, 10, seed=3000, gaits=("trot10",), robots=("a1",))
+    eng = LinearMpc(horizon=10, robot="a1", device="cuda:0")
+    res = eng.solve(bt["x0"], bt["xref"], bt["contact"], bt["feet"], robot=bt["robot"], return_all=True)
+    ref = res.u0.cpu().numpy()
+    err = float(np.abs(got["u0"] - ref).max() / np.abs(ref).max())
+    print(f"dumped u0 vs in-process solve: rel err {err:.3e}")
+    assert err <= 1e-5
+    assert np.array_equal(got["iterations"], res.iterations.cpu().numpy().astype(np.float32))
+
+
 def test_bench_config1_drop_in_latency():
     """Config 1: the drop-in controller's per-tick latency line (B = 1, horizon 16)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "config1", "--steps", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "config1", "--steps", "5",
                           "--warmup", "2", "--cpu-seconds", "0.5"], capture_output=True, text=True, timeout=600,
                          check=True)
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -91,7 +124,7 @@ def test_bench_two_ranks_real_engine():
     line's key set, the CPU baseline included."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MPCQP_BENCH_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4",
                           "--warmup", "1", "--cpu-seconds", "0.5", "--no-callers", "--event-every", "1"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-4000:]

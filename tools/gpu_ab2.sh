@@ -27,9 +27,9 @@ for spec in "$@"; do
     cc=$c; extra=""
     [ $c = config4s ] && { cc=config4; extra="--standing-every 1"; steps=8; }
     if [ "$lib" = default ]; then
-      out=$(timeout -k 10 180 python bench.py --no-cpu --no-callers --no-hint-line --config $cc $extra --steps $steps --warmup 2) || exit 1
+      out=$(timeout -k 10 180 python bench.py --full --no-cpu --no-callers --no-hint-line --config $cc $extra --steps $steps --warmup 2) || exit 1
     else
-      out=$(MPCQP_LIB=$lib timeout -k 10 180 python bench.py --no-cpu --no-callers --no-hint-line --config $cc $extra --steps $steps --warmup 2) || exit 1
+      out=$(MPCQP_LIB=$lib timeout -k 10 180 python bench.py --full --no-cpu --no-callers --no-hint-line --config $cc $extra --steps $steps --warmup 2) || exit 1
     fi
     echo "$lib $c $(echo "$out" | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%.3f MQP/s kernel %.4f ms frac %.3f iters %.1f/%d ok %.3f" % (d["value"]/1e6, d["kernel_ms_avg"], (d["roofline"]["frac"] or 0), d["iters_mean"], d["iters_max"], d["status_ok_frac"]))')"
   done

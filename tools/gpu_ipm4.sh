@@ -13,9 +13,9 @@ rc=$?; tail -3 $O/tests.log
 for lib in default tools/lib_ipm3cu.so; do
   for rep in 1 2; do
     if [ $lib = default ]; then E=""; else E="MPCQP_LIB=$lib"; fi
-    env $E timeout -k 10 200 python3 bench.py --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --steps 10 --warmup 2 > $O/c4s_$rep.json || exit $?
-    env $E timeout -k 10 200 python3 bench.py --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --warm-fleet --steps 12 --warmup 2 > $O/c4sw_$rep.json || exit $?
-    env $E timeout -k 10 200 python3 bench.py --config config1 --gait standing --steps 40 --warmup 5 --no-cpu > $O/c1s_$rep.json || exit $?
+    env $E timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --steps 10 --warmup 2 > $O/c4s_$rep.json || exit $?
+    env $E timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --warm-fleet --steps 12 --warmup 2 > $O/c4sw_$rep.json || exit $?
+    env $E timeout -k 10 200 python3 bench.py --full --config config1 --gait standing --steps 40 --warmup 5 --no-cpu > $O/c1s_$rep.json || exit $?
     python3 - "$lib" "$O" "$rep" <<'PY'
 import json, sys
 lib, o, rep = sys.argv[1:]

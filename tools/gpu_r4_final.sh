@@ -13,17 +13,17 @@ mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 240 --timeout-method thread > $O/tests.log 2>&1
 rc=$?; tail -3 $O/tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc $rc: stopping"; exit $rc; fi
-timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json || exit $?
-timeout -k 10 200 python3 bench.py --steps 200 --warmup 20 > $O/bench.json || exit $?
+timeout -k 10 200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json || exit $?
+timeout -k 10 200 python3 bench.py --full --steps 200 --warmup 20 > $O/bench.json || exit $?
 for c in config3 config4 config5; do
-  timeout -k 10 200 python3 bench.py --no-cpu --no-callers --config $c > $O/bench_$c.json || exit $?
+  timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --config $c > $O/bench_$c.json || exit $?
 done
-timeout -k 10 200 python3 bench.py --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --steps 10 --warmup 2 > $O/bench_config4_standing1.json || exit $?
-timeout -k 10 200 python3 bench.py --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --warm-fleet --steps 12 --warmup 2 > $O/bench_config4_standing1_warm.json || exit $?
-timeout -k 10 200 python3 bench.py --no-cpu --no-callers --config config4 --standing-every 16 --steps 40 --warmup 4 > $O/bench_config4_standing16.json || exit $?
-timeout -k 10 300 python3 bench.py --no-cpu --no-callers --config config5 --standing-every 16 --steps 20 --warmup 2 > $O/bench_config5_standing16.json || exit $?
-timeout -k 10 200 python3 bench.py --config config1 --cpu-seconds 4 > $O/c1_trot.json || exit $?
-timeout -k 10 200 python3 bench.py --config config1 --gait standing --steps 100 --warmup 10 --cpu-seconds 4 > $O/c1_standing.json || exit $?
+timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --steps 10 --warmup 2 > $O/bench_config4_standing1.json || exit $?
+timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --no-hint-line --config config4 --standing-every 1 --warm-fleet --steps 12 --warmup 2 > $O/bench_config4_standing1_warm.json || exit $?
+timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --config config4 --standing-every 16 --steps 40 --warmup 4 > $O/bench_config4_standing16.json || exit $?
+timeout -k 10 300 python3 bench.py --full --no-cpu --no-callers --config config5 --standing-every 16 --steps 20 --warmup 2 > $O/bench_config5_standing16.json || exit $?
+timeout -k 10 200 python3 bench.py --full --config config1 --cpu-seconds 4 > $O/c1_trot.json || exit $?
+timeout -k 10 200 python3 bench.py --full --config config1 --gait standing --steps 100 --warmup 10 --cpu-seconds 4 > $O/c1_standing.json || exit $?
 python3 - "$O" <<'PY'
 import json, sys, glob, os
 o = sys.argv[1]

@@ -9,10 +9,10 @@ mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 240 --timeout-method thread > $O/tests.log 2>&1
 rc=$?; tail -3 $O/tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc $rc: stopping"; exit $rc; fi
-timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json || exit $?
-timeout -k 10 200 python3 bench.py --no-cpu --no-callers --steps 200 --warmup 20 > $O/bench.json || exit $?
+timeout -k 10 200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json || exit $?
+timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --steps 200 --warmup 20 > $O/bench.json || exit $?
 for c in config3 config4 config5; do
-  timeout -k 10 200 python3 bench.py --no-cpu --no-callers --config $c > $O/bench_$c.json || exit $?
+  timeout -k 10 200 python3 bench.py --full --no-cpu --no-callers --config $c > $O/bench_$c.json || exit $?
 done
 python3 - "$O" <<'PY'
 import json, sys, glob, os

@@ -15,16 +15,16 @@ for rep in 1 2; do
   for c in config2 config3 config4 config5; do
     steps=100; [ $c = config5 ] && steps=30
     for o in 0 1; do
-      out=$(timeout -k 10 180 python bench.py --no-cpu --no-callers --no-hint-line --config $c --steps $steps --warmup 5 --order $o) || exit 1
+      out=$(timeout -k 10 180 python bench.py --full --no-cpu --no-callers --no-hint-line --config $c --steps $steps --warmup 5 --order $o) || exit 1
       echo "default order=$o $c $(echo "$out" | line)" | tee -a $O/ab_order.txt
     done
   done
   for lib in "$@"; do
     for c in config2 config3; do
-      out=$(MPCQP_LIB=$lib timeout -k 10 180 python bench.py --no-cpu --no-callers --no-hint-line --config $c --steps 100 --warmup 5 --order 1) || exit 1
+      out=$(MPCQP_LIB=$lib timeout -k 10 180 python bench.py --full --no-cpu --no-callers --no-hint-line --config $c --steps 100 --warmup 5 --order 1) || exit 1
       echo "$lib order=1 $c $(echo "$out" | line)" | tee -a $O/ab_order.txt
     done
   done
 done
-timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json || exit $?
+timeout -k 10 200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json || exit $?
 echo "driver cmd $(cat $O/bench_driver_cmd.json | line)"

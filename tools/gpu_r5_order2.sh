@@ -3,6 +3,7 @@
 # kernel's own time (kernel trace of config 4 / 5), and the solo-vs-shared stamps of config 2
 #   gpurun -- 'TAG=r5_order2 bash tools/gpu_r5_order2.sh'
 set -o pipefail
+REPO=$(cd "$(dirname "$0")/.." && pwd)   # the repository root
 cd $GRAFT_REPO_ROOT
 TAG=${TAG:?set TAG}
 O=gpurun_out/$TAG
@@ -15,7 +16,7 @@ for rep in 1 2; do
   for c in config3 config4 config5; do
     steps=100; [ $c = config5 ] && steps=30
     for o in 0 1; do
-      out=$(timeout -k 10 180 python bench.py --no-cpu --no-callers --no-hint-line --config $c --steps $steps --warmup 5 --order $o) || exit 1
+      out=$(timeout -k 10 180 python bench.py --full --no-cpu --no-callers --no-hint-line --config $c --steps $steps --warmup 5 --order $o) || exit 1
       echo "order=$o $c $(echo "$out" | line)" | tee -a $O/ab_order.txt
     done
   done
@@ -23,7 +24,7 @@ done
 cd /tmp && export TMPDIR=/tmp
 for c in config4 config5; do
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/kt_$c -o kt --output-format csv -- \
-    python3 $GRAFT_REPO_ROOT/bench.py --no-cpu --no-callers --no-hint-line --config $c --steps 10 --warmup 2 > $GRAFT_REPO_ROOT/$O/kt_$c.json || exit 1
+    python3 $REPO/bench.py --full --no-cpu --no-callers --no-hint-line --config $c --steps 10 --warmup 2 > $REPO/$O/kt_$c.json || exit 1
 done
 cd $GRAFT_REPO_ROOT
 grep -h "order_kernel\|kernel_96\|kernel_128" $O/kt_*/kt_kernel_stats.csv | cut -d, -f1-4 | sed 's/((anonymous[^"]*//' | tee $O/order_kernel_time.txt

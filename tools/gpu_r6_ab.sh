@@ -5,6 +5,7 @@
 # (class 128) and config 2 (class 64).  TESTS=1 runs the GPU suite (in-tree library) first.
 #   gpurun -- 'TESTS=1 SQ=1 bash tools/gpu_r6_ab.sh tools/lib_base.so tools/lib_x.so'
 set -o pipefail
+REPO=$(cd "$(dirname "$0")/.." && pwd)   # the repository root
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${TAG:-r6ab}
 mkdir -p $O
@@ -28,7 +29,7 @@ for rep in 1 2; do
 for lib in "$@"; do
   for c in $CONFIGS; do
     steps=100; [ $c = config5 ] && steps=30
-    out=$(MPCQP_LIB=$lib timeout -k 10 180 python bench.py --no-cpu --no-callers --no-hint-line --config $c --steps $steps --warmup 5) || exit 1
+    out=$(MPCQP_LIB=$lib timeout -k 10 180 python bench.py --full --no-cpu --no-callers --no-hint-line --config $c --steps $steps --warmup 5) || exit 1
     echo "$lib $c $(echo "$out" | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%.3f MQP/s kernel %.4f ms frac %.3f iters %.1f/%d ok %.3f" % (d["value"]/1e6, d["kernel_ms_avg"], (d["roofline"]["frac"] or 0), d["iters_mean"], d["iters_max"], d["status_ok_frac"]))')"
   done
 done
@@ -42,7 +43,7 @@ if [ "${SQ:-0}" = 1 ]; then
     for c in config5 config2; do
       d=$GRAFT_REPO_ROOT/$O/sq_${i}_$c
       MPCQP_LIB=$GRAFT_REPO_ROOT/$lib timeout -s KILL 120 rocprofv3 --pmc $SET -d $d -o pmc --output-format csv -- \
-        python3 $GRAFT_REPO_ROOT/bench.py --no-cpu --no-callers --no-hint-line --steps 5 --warmup 1 --config $c > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
+        python3 $REPO/bench.py --full --no-cpu --no-callers --no-hint-line --steps 5 --warmup 1 --config $c > $d.json 2> $d.err || { tail -5 $d.err; exit 1; }
       echo "== SQ $lib $c"
       python3 $GRAFT_REPO_ROOT/tools/sq_summary.py $d | grep -A9 -E "^k(64|128)"
     done

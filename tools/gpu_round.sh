@@ -5,12 +5,13 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 TAG=${TAG:?set TAG}
-mkdir -p gpurun_out
-timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > gpurun_out/${TAG}_tests.log 2>&1 || { tail -30 gpurun_out/${TAG}_tests.log; exit 1; }
-tail -1 gpurun_out/${TAG}_tests.log
-timeout -k 10 200 python bench.py > gpurun_out/${TAG}_bench.json || exit 1
+export RUN_OUT=${RUN_OUT:-run_out}   # where this script writes
+mkdir -p $RUN_OUT
+timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $RUN_OUT/${TAG}_tests.log 2>&1 || { tail -30 $RUN_OUT/${TAG}_tests.log; exit 1; }
+tail -1 $RUN_OUT/${TAG}_tests.log
+timeout -k 10 200 python bench.py --full > $RUN_OUT/${TAG}_bench.json || exit 1
 for c in config3 config4 config5; do
-  timeout -k 10 200 python bench.py --no-cpu --config $c > gpurun_out/${TAG}_bench_$c.json || exit 1
+  timeout -k 10 200 python bench.py --full --no-cpu --config $c > $RUN_OUT/${TAG}_bench_$c.json || exit 1
 done
 bash tools/profile.sh ${TAG} || exit 1
-cat gpurun_out/${TAG}_bench.json
+cat $RUN_OUT/${TAG}_bench.json
