@@ -74,6 +74,13 @@ struct KParams {
     stamps_[i] = __builtin_amdgcn_s_memtime();  \
     __builtin_amdgcn_sched_barrier(0);          \
   } while (0)
+// sub-stamps of the first phase (stage, stance, model; slots 9..11 of the stamp buffer)
+#define SUBSTAMP(i)                               \
+  do {                                            \
+    __builtin_amdgcn_sched_barrier(0);            \
+    substamps_[i] = __builtin_amdgcn_s_memtime(); \
+    __builtin_amdgcn_sched_barrier(0);            \
+  } while (0)
 // section accumulators live one per lane (lane k holds section k): a uniform
 // compare, no runtime-indexed private array (that would go to scratch, and the
 // next barrier's vmcnt wait would absorb the scratch latency)
@@ -102,6 +109,9 @@ constexpr unsigned kDiagLds = 0;
   } while (0)
 #define STAMP(i) \
   do {           \
+  } while (0)
+#define SUBSTAMP(i) \
+  do {              \
   } while (0)
 #define SEC(k) \
   do {         \

@@ -96,10 +96,16 @@ __device__ __forceinline__ bool fany(bool v) {
 }
 
 // Stage the robot's inputs in LDS; false if any is non-finite (status NONFINITE).
-template <int NT, class F>
+// `pre` (class 64): work that needs none of the inputs, run between the issue of a thread's
+// first chunk load and its use, i.e. under the global-load latency.
+struct StageNoPre {
+  __device__ void operator()() const {}
+};
+template <int NT, class F, class Pre>
 __device__ __forceinline__ bool form_stage(F& f, int N, int b, int tid, const float* __restrict__ x0g,
                                            const float* __restrict__ xrefg, const float* __restrict__ contactg,
-                                           const float* __restrict__ feetg, const float* __restrict__ robotg) {
+                                           const float* __restrict__ feetg, const float* __restrict__ robotg,
+                                           Pre&& pre) {
   // The robot's five input slices, staged into LDS with 16-byte loads: each slice is
   // covered by the 16-byte-aligned chunks that hold it (a chunk never crosses a page,
   // so the few bytes of the neighbouring robots it also holds are always readable),
@@ -119,32 +125,58 @@ __device__ __forceinline__ bool form_stage(F& f, int N, int b, int tid, const fl
   const int c1 = nchunks(p0, NX), c2 = c1 + nchunks(p1, 12), c3 = c2 + nchunks(p2, MPCQP_ROBOT_STRIDE),
             c4 = c3 + nchunks(p3, 4 * N), c5 = c4 + nchunks(p4, NX * N);
   int bad = 0;
-  for (int c = tid; c < c5; c += NT) {
+  struct Chunk {
+    float4 v;
+    int i, e;   // slice; slice index of v.x (may be < 0)
+  };
+  auto load = [&](int c) -> Chunk {
     const int i = (c >= c1) + (c >= c2) + (c >= c3) + (c >= c4);
     const float* const q = i == 0 ? p0 : i == 1 ? p1 : i == 2 ? p2 : i == 3 ? p3 : p4;
     const int cb = i == 0 ? 0 : i == 1 ? c1 : i == 2 ? c2 : i == 3 ? c3 : c4;
+    const uintptr_t base = ((uintptr_t)q & ~(uintptr_t)15) + 16 * (uintptr_t)(c - cb);
+    return Chunk{*reinterpret_cast<const float4*>(base), i, (int)(((intptr_t)base - (intptr_t)q) >> 2)};
+  };
+  auto store = [&](const Chunk& k) {
+    const int i = k.i;
     const int len = i == 0 ? NX : i == 1 ? 12 : i == 2 ? 12 : i == 3 ? 4 * N : NX * N;   // robot: 12 fields read
     const int dst = i == 0 ? IN_X0 : i == 1 ? IN_FEET : i == 2 ? IN_ROBOT : i == 3 ? IN_CONTACT : F::IN_XREF;
-    const uintptr_t base = ((uintptr_t)q & ~(uintptr_t)15) + 16 * (uintptr_t)(c - cb);
-    const float4 v = *reinterpret_cast<const float4*>(base);
-    const int e = (int)(((intptr_t)base - (intptr_t)q) >> 2);   // slice index of v.x (may be < 0)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float w = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
-      const int k = e + j;
-      if (k >= 0 && k < len) {
-        in[dst + k] = w;
+      const float w = j == 0 ? k.v.x : j == 1 ? k.v.y : j == 2 ? k.v.z : k.v.w;
+      const int kk = k.e + j;
+      if (kk >= 0 && kk < len) {
+        in[dst + kk] = w;
         bad |= i != 3 && !isfinite(w);   // contact is not checked
       }
     }
+  };
+  if constexpr (!std::is_same_v<std::decay_t<Pre>, StageNoPre>) {
+    int c = tid;
+    Chunk k{float4{0.f, 0.f, 0.f, 0.f}, 0, 0};
+    if (c < c5) k = load(c);
+    pre();
+    while (c < c5) {
+      store(k);
+      c += NT;
+      if (c < c5) k = load(c);
+    }
+  } else {
+    for (int c = tid; c < c5; c += NT) store(load(c));
   }
   return !fany<NT>(bad != 0);
 }
+template <int NT, class F>
+__device__ __forceinline__ bool form_stage(F& f, int N, int b, int tid, const float* __restrict__ x0g,
+                                           const float* __restrict__ xrefg, const float* __restrict__ contactg,
+                                           const float* __restrict__ feetg, const float* __restrict__ robotg) {
+  return form_stage<NT>(f, N, b, tid, x0g, xrefg, contactg, feetg, robotg, StageNoPre{});
+}
 
 // Stance list from the gait table (one wave: lanes cover 4N <= 128 entries).
-// Returns S (wave-uniform).  Writes meta.{foot_t, foot_leg, ub, stance_of, S}.
+// Returns S (wave-uniform).  Writes meta.{foot_t, foot_leg, ub, stance_of, S} when `write`
+// (class 64: every wave counts S for itself, wave 0 writes the lists).
 template <class F, class MT>
-__device__ __forceinline__ int form_stance(const F& f, MT& mt, int N, int lane) {
+__device__ __forceinline__ int form_stance(const F& f, MT& mt, int N, int lane, bool write = true) {
   const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   const int nk = 4 * N;
   const float c0 = lane < nk ? f.in[IN_CONTACT + lane] : 0.f;
@@ -153,6 +185,7 @@ __device__ __forceinline__ int form_stance(const F& f, MT& mt, int N, int lane) 
   const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1);
   const int S0 = __popcll(m0);
   const int S = uni(S0 + __popcll(m1));
+  if (!write) return S;
   const int i0 = __popcll(m0 & lt_mask), i1 = S0 + __popcll(m1 & lt_mask);
   const double fzmax = (double)f.in[IN_ROBOT + 8];
   if (lane < nk) mt.stance_of[lane] = f0 ? i0 : -1;
@@ -257,18 +290,43 @@ __device__ __forceinline__ void form_model_full(const KParams& P, F& f, FormY& f
   }
 }
 
+// The weights' staged copies (state weights, 2 R_ii; kernel arguments indexed per lane are memory loads)
+template <class F>
+__device__ __forceinline__ void form_weights(const KParams& P, F& f, FormY& fy, int tid) {
+  if (tid < NX) f.q[tid] = P.q[tid];
+  if (tid < NU) fy.rd2[tid] = 2.0 * P.r[tid];
+}
+
 // Model (float32-faithful), cone rows, Ya/Yb, horizon suffix sums.  All NT threads.
-template <int NT, class F, class MT>
+// SPLIT (class 64, two waves): the 3 x 3 chain R_z I_B -> I_w ->
+// inv(I_w) -> K, G passes through LDS inside wave 0 (wave fences, no workgroup barrier) while
+// wave 1, which needs none of it, builds the cone rows and the horizon suffix sums: ONE
+// workgroup barrier between the staged inputs and the Ya/Yb loop.
+template <int NT, bool SPLIT = false, class F, class MT>
 __device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT& mt, int N, int tid) {
+  static_assert(!SPLIT || NT == 2 * LANES, "the split setup is laid out for two waves");
+  constexpr int CS = SPLIT ? LANES : NT;   // threads the chain's syncs cover
+  // first thread of the suffix sums (13 threads) and of the cone rows (18 threads)
+  constexpr int T_SUF = SPLIT ? LANES : 64 - 16;
+  constexpr int T_CONE = SPLIT ? 2 * LANES - 18 : 64 - 18;
   const float* const rbs = f.in + IN_ROBOT;
   const double h = P.dt;
+  // SPLIT: wave 1's suffix-sum threads cannot wait for wave 0's staged copy (f.q): each loads
+  // its own weight, here, so that the load flies under cos / sin
+  double qsuf = 0.0;
+  if constexpr (SPLIT)
+    if (tid >= T_SUF && tid < T_SUF + NX) qsuf = P.q[tid - T_SUF];
   // ---- R_z, I_w = float32(float32(R_z I_B) R_z^T), inverse (mpc.py:178-182)
   const double yaw = (double)f.in[IN_X0 + 2];
-  const double c = f32r(cos(yaw)), s = f32r(sin(yaw));
+  // one sincos: half the instructions of cos and sin apart (the compiler does not merge their
+  // argument reductions), the same values
+  double sy, cy;
+  sincos(yaw, &sy, &cy);
+  const double c = f32r(cy), s = f32r(sy);
   auto rz = [&](int a, int bb) -> double {   // R_z[a][bb] (kinematics rot_z, float32 entries)
     return a == 2 ? (bb == 2 ? 1.0 : 0.0) : (bb == 2 ? 0.0 : (a == bb ? c : (a == 0 ? -s : s)));
   };
-  {
+  if (!SPLIT || tid < LANES) {
     const int i = tid / 3, j = tid % 3;
     auto ib = [&](int a, int bb) -> double {
       const int lo = a < bb ? a : bb, hi = a < bb ? bb : a;
@@ -276,18 +334,18 @@ __device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT
       return (double)rbs[1 + idx];
     };
     if (tid < 9) f.ii[tid] = f32r(rz(i, 0) * ib(0, j) + rz(i, 1) * ib(1, j) + rz(i, 2) * ib(2, j));
-    if (tid < NX) f.q[tid] = P.q[tid];
+    form_weights(P, f, fy, tid);
     if (tid == 0) {
       f.rz[0] = c;
       f.rz[1] = s;
       f.minv = f32r(1.0 / (double)rbs[0]);   // I / m in float32 (mpc.py:190)
     }
-    fsync<NT>();
+    fsync<CS>();
     double iw = 0.0;
     if (tid < 9) iw = f32r(f.ii[3 * i] * rz(j, 0) + f.ii[3 * i + 1] * rz(j, 1) + f.ii[3 * i + 2] * rz(j, 2));
-    fsync<NT>();
+    fsync<CS>();
     if (tid < 9) f.ii[tid] = iw;
-    fsync<NT>();
+    fsync<CS>();
     if (tid < 9) {   // 3x3 inverse by adjugate (float64), stored float32 like np.linalg.inv
       const double* I = f.ii;
       const int r1 = (j + 1) % 3, r2 = (j + 2) % 3, c1 = (i + 1) % 3, c2 = (i + 2) % 3;
@@ -296,12 +354,27 @@ __device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT
                          I[2] * (I[3] * I[7] - I[4] * I[6]);
       iw = f32r(cof / det);
     }
-    fsync<NT>();
+    fsync<CS>();
     if (tid < 9) f.ii[tid] = iw;
+    fsync<CS>();
+    // ---- K = float32(inv(I_w) [r]x) (mpc.py:188-189) and G = R_z^T K; thread (i, col)
+    if (tid < 36) {
+      const int i = tid / NU, col = tid % NU, leg = col / 3, j = col % 3;
+      const float* fb = f.in + IN_FEET;
+      const double rx = fb[3 * leg], ry = fb[3 * leg + 1], rzz = fb[3 * leg + 2];
+      const double sk0 = (j == 0) ? 0.0 : (j == 1 ? -rzz : ry);   // column j of [r]x
+      const double sk1 = (j == 0) ? rzz : (j == 1 ? 0.0 : -rx);
+      const double sk2 = (j == 0) ? -ry : (j == 1 ? rx : 0.0);
+      double kk[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) kk[a] = f32r(f.ii[3 * a] * sk0 + f.ii[3 * a + 1] * sk1 + f.ii[3 * a + 2] * sk2);
+      f.K[i][col] = kk[i];
+      f.G[i][col] = rz(0, i) * kk[0] + rz(1, i) * kk[1] + rz(2, i) * kk[2];
+    }
   }
   // ---- friction-cone rows in the (t1, t2, n) frame (mpc.py:239-245 for n = e_z)
-  if (tid >= 64 - 18 && tid < 64) {
-    const int k18 = tid - (64 - 18);
+  if (tid >= T_CONE && tid < T_CONE + 18) {
+    const int k18 = tid - T_CONE;
     double nx = rbs[9], ny = rbs[10], nz = rbs[11];
     const double nn = sqrt(nx * nx + ny * ny + nz * nz);
     if (!(nn > 0.0)) {
@@ -326,31 +399,15 @@ __device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT
     mt.rows[rr][k] = val;
     if (k18 == 0) mt.fz0_implied = mu > 0.0;
   }
-  fsync<NT>();
-  // ---- K = float32(inv(I_w) [r]x) (mpc.py:188-189) and G = R_z^T K; thread (i, col)
-  if (tid < 36) {
-    const int i = tid / NU, col = tid % NU, leg = col / 3, j = col % 3;
-    const float* fb = f.in + IN_FEET;
-    const double rx = fb[3 * leg], ry = fb[3 * leg + 1], rzz = fb[3 * leg + 2];
-    const double sk0 = (j == 0) ? 0.0 : (j == 1 ? -rzz : ry);   // column j of [r]x
-    const double sk1 = (j == 0) ? rzz : (j == 1 ? 0.0 : -rx);
-    const double sk2 = (j == 0) ? -ry : (j == 1 ? rx : 0.0);
-    double kk[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) kk[a] = f32r(f.ii[3 * a] * sk0 + f.ii[3 * a + 1] * sk1 + f.ii[3 * a + 2] * sk2);
-    f.K[i][col] = kk[i];
-    f.G[i][col] = rz(0, i) * kk[0] + rz(1, i) * kk[1] + rz(2, i) * kk[2];
-  }
-  // ---- horizon suffix sums of Q e_t and t Q e_t; thread s (state component)
-  if (tid < NU) fy.rd2[tid] = 2.0 * P.r[tid];
   if (P.wfull) {
     form_model_full<NT>(P, f, fy, N, tid);
     return;
   }
-  if (tid >= 64 - 16 && tid < 64 - 16 + NX) {
-    const int sc = tid - (64 - 16);
+  // ---- horizon suffix sums of Q e_t and t Q e_t; thread s (state component)
+  if (tid >= T_SUF && tid < T_SUF + NX) {
+    const int sc = tid - T_SUF;
     const float* xin = f.in + IN_X0;
-    const double q = f.q[sc];
+    const double q = SPLIT ? qsuf : f.q[sc];
     // n1 = Nm x0, n2 = Nm^2 x0 (closed form of the 13x13 products)
     double x0s = (double)xin[sc], n1 = 0.0, n2 = 0.0;
     const double g12 = (double)xin[12];

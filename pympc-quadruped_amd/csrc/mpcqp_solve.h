@@ -202,6 +202,7 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
   const int N = P.N;
 #ifdef MPCQP_STAMPS
   unsigned long long stamps_[7];
+  unsigned long long substamps_[3] = {0, 0, 0};
   unsigned long long secacc_ = 0, seclast_ = 0;
   int seccur_ = 7;
 #endif
@@ -213,13 +214,45 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
   // ------------------------------------------------ inputs, stance list
   Form& smf = sm.fa.f;
   FormY& smfy = sm.fa.fy;
-  if (!form_stage<NT>(smf, N, b, tid, x0g, xrefg, contactg, feetg, robotg)) {
+  // Class 64 (four robots per CU, its setup a quarter of the launch) splits the setup over
+  // its two waves and keeps it to two workgroup barriers; classes 96 / 128 keep the plain
+  // sequence (no SGPRs to spare for it)
+  constexpr bool kSplitSetup = NV == 64;
+  // the H build's integer block weights, once per step pair instead of once per entry
+  auto fill_mt_tab = [&] {
+    if constexpr (!FULL) {
+      for (int e = tid; e < N * N; e += NT) {
+        const int ja = e / N, jb = e - ja * N;
+        const int mx = ja > jb ? ja : jb;
+        const int d = ja > jb ? ja - jb : jb - ja;
+        const int m = N - mx;
+        const int ta = (m * (4 * m * m - 1)) / 3 + 2 * d * m * m;   // exact integer
+        sm.fa.mt_tab[e] = d2{(double)ta, (double)m};
+      }
+    }
+  };
+  bool staged;
+  if constexpr (kSplitSetup) {
+    // the table needs no input: it is written while the inputs load
+    staged = form_stage<NT>(smf, N, b, tid, x0g, xrefg, contactg, feetg, robotg, fill_mt_tab);
+  } else {
+    staged = form_stage<NT>(smf, N, b, tid, x0g, xrefg, contactg, feetg, robotg);
+  }
+  if (!staged) {
     write_empty_t<NT>(b, tid, N, MPCQP_STATUS_NONFINITE, u0g, Ug, statusg, itersg);
     return;
   }
-  if (wave == 0) form_stance(smf, sm.mt, N, lane);
-  fsync<NT>();
-  const int S = uni(sm.mt.S);
+  SUBSTAMP(0);
+  // split: every wave counts the stance foot-steps for itself (no barrier); wave 0 writes the
+  // lists, which wave 1 reads behind form_model's barrier
+  int S;
+  if constexpr (kSplitSetup) {
+    S = form_stance(smf, sm.mt, N, lane, wave == 0);
+  } else {
+    if (wave == 0) form_stance(smf, sm.mt, N, lane);
+    fsync<NT>();
+    S = uni(sm.mt.S);
+  }
   const int n = 3 * S, m = 6 * S;
   if (n > NV) {
     // the next capacity class takes it: `queue`, `queue_big` (when given) for a robot
@@ -236,20 +269,22 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
   }
 
   // ------------------------------------------------ formulation (mpcqp_form.h)
-  form_model<NT>(P, smf, smfy, sm.mt, N, tid);
-  if constexpr (!FULL) {
-    // the H build's integer block weights, once per step pair instead of once per entry
-    for (int e = tid; e < N * N; e += NT) {
-      const int ja = e / N, jb = e - ja * N;
-      const int mx = ja > jb ? ja : jb;
-      const int d = ja > jb ? ja - jb : jb - ja;
-      const int m = N - mx;
-      const int ta = (m * (4 * m * m - 1)) / 3 + 2 * d * m * m;   // exact integer
-      sm.fa.mt_tab[e] = d2{(double)ta, (double)m};
+  SUBSTAMP(1);
+  form_model<NT, kSplitSetup>(P, smf, smfy, sm.mt, N, tid);
+  SUBSTAMP(2);
+  if constexpr (kSplitSetup) {
+    // g needs K, G and the suffix sums, all behind form_model's barrier, not its Ya/Yb: wave 1
+    // takes it (wave 0 has the Ya/Yb loop's second trip)
+    if (tid >= NT - NV) {
+      const int a = tid - (NT - NV);
+      sm.gv[a] = a < n ? form_g(P, smf, sm.mt, a) : 0.0;
     }
+    fsync<NT>();   // Ya/Yb, g
+  } else {
+    fill_mt_tab();
+    fsync<NT>();
+    if (tid < NV) sm.gv[tid] = tid < n ? form_g(P, smf, sm.mt, tid) : 0.0;
   }
-  fsync<NT>();
-  if (tid < NV) sm.gv[tid] = tid < n ? form_g(P, smf, sm.mt, tid) : 0.0;
   STAMP(1);
 
   // row `r` of the lane's H tile (identity padding beyond n); cj / cc: the tile
@@ -474,13 +509,19 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
   if (lane == 0) sm.wmax[wave] = wd;
   // the foot-steps' 3x3 diagonal blocks of W, for the rows' dual-curvature scales below
   fsync<NT>();   // every lane is done reading the last pivot column (wb aliases zc)
+  // Row `row` of foot-step sf holds its block's entries in the tile columns c0, c0 + 1, c0 + 2,
+  // c0 = 3 sf - TW tc (n is a multiple of 3: row < n puts the block's columns below n too);
+  // they go to wb[9 sf + 3 (row % 3) + c - c0], one window test and a fixed offset per entry
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
+  for (int r = 0; r < 4; ++r) {
+    const int row = 4 * tr + r;
+    const int sf = row / 3;
+    const int c0 = row < n ? 3 * sf - TW * tc : NV;   // NV: no column of the tile
+    const int wi = 9 * sf + 3 * (row - 3 * sf) - c0;
 #pragma unroll
-    for (int c = 0; c < TW; ++c) {
-      const int row = 4 * tr + r, col = TW * tc + c;
-      if (row < n && col < n && row / 3 == col / 3) sm.wb[9 * (row / 3) + 3 * (row % 3) + col % 3] = W[r][c];
-    }
+    for (int c = 0; c < TW; ++c)
+      if ((unsigned)(c - c0) < 3u) sm.wb[wi + c] = W[r][c];
+  }
   STAMP(3);
 
   // unconstrained minimiser x = -W g
@@ -1169,7 +1210,7 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
 
 #ifdef MPCQP_STAMPS
   // stamps build: U is a diagnostic buffer of kStampU64 u64 per robot (tools/phase_stamps.py):
-  // [0, 7) phase stamps, 7 / 8 chip-wide start / end (s_memrealtime), [16, 24) each wave's HW_ID,
+  // [0, 7) phase stamps, 7 / 8 chip-wide start / end (s_memrealtime), [9, 12) sub-stamps, [16, 24) each wave's HW_ID,
   // [32 + 24 w, 56 + 24 w) wave w's section accumulators and event counters (lane k: section k)
   if (Ug) {
     unsigned long long* dst = (unsigned long long*)Ug + (size_t)b * kStampU64;
@@ -1177,6 +1218,7 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
       for (int i = 0; i < 7; ++i) dst[i] = stamps_[i];
       dst[7] = rt0_;
       dst[8] = __builtin_amdgcn_s_memrealtime();
+      for (int i = 0; i < 3; ++i) dst[9 + i] = substamps_[i];
     }
     if (lane < 24) dst[32 + 24 * wave + lane] = secacc_;
     if (lane == 0)   // SIMD, CU, SE; XCC_ID; workgroup id

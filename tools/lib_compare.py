@@ -2,7 +2,9 @@
 u0 / iterations / status (compare two libraries with two runs):
   MPCQP_LIB=tools/libB.so python tools/lib_compare.py out.npz [B] [N] [gaits]
 (LC_RANGE=lo,hi: promise the stance range, e.g. 64,64 for an all-standing N = 16 fleet;
-LC_STAND=1: every robot standing)"""
+LC_STAND=1: every robot standing; LC_ROBOTS=a1,aliengo and LC_TILT=15: the robot presets and the
+surface-normal tilt of bench.py's config 5).  With a reference file the last line says whether
+u0, U, iterations and status are bitwise those of the reference."""
 import os
 import sys
 
@@ -21,7 +23,8 @@ def main():
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
     N = int(sys.argv[3]) if len(sys.argv) > 3 else 10
     gaits = tuple(sys.argv[4].split(",")) if len(sys.argv) > 4 else ("trot10",)
-    bt = make_batch(B, N, seed=1000, gaits=gaits, robots=("a1",))
+    robots = tuple(os.environ.get("LC_ROBOTS", "a1").split(","))
+    bt = make_batch(B, N, seed=1000, gaits=gaits, robots=robots, tilt_deg=float(os.environ.get("LC_TILT", "0")))
     if os.environ.get("LC_STAND"):
         bt["contact"][:] = 1.0
     eng = LinearMpc(horizon=N, robot="a1", device="cuda:0")
@@ -41,6 +44,9 @@ def main():
         worst = np.argsort(du)[-5:]
         print("u0 rel diff max %.2e; worst robots %s" % (du.max(), [(int(i), float(du[i]), int(it0[i]), int(it1[i])) for i in worst]))
         print("status ref", np.bincount(ref["st"]), "this", np.bincount(res.status.cpu().numpy()))
+        same = {k: bool(np.array_equal(ref[k], v.cpu().numpy())) for k, v in
+                (("u0", res.u0), ("U", res.U), ("it", res.iterations), ("st", res.status))}
+        print("bitwise equal to the reference:", same, "ALL EQUAL" if all(same.values()) else "DIFFERENT")
 
 
 if __name__ == "__main__":

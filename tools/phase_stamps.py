@@ -2,7 +2,8 @@
 
 Uses a separately built libmpcqp_stamps.so (-DMPCQP_STAMPS, `python tools/phase_stamps.py build`)
 whose kernels write, per robot, into the U buffer taken as 256 u64 slots (mpcqp_solve.h):
-[0, 7) phase stamps, 7 / 8 chip-wide start / end (s_memrealtime, 100 MHz), [16, 24) each wave's
+[0, 7) phase stamps, 7 / 8 chip-wide start / end (s_memrealtime, 100 MHz), [9, 12) sub-stamps of
+the first phase (after staging, after the stance list, after the model), [16, 24) each wave's
 HW_ID, [32 + 24 w, 56 + 24 w) wave w's section accumulators (lane k: section k) and event
 counters.  The shipped library executes no stamp.  Prints median / max cycles per phase and, per
 wave, the active set's cycles per iteration by section.
@@ -20,6 +21,8 @@ sys.path.insert(0, os.path.join(ROOT, "pympc-quadruped_amd"))
 STAMPS_LIB = os.path.join(ROOT, "pympc-quadruped_amd", "mpcqp", "libmpcqp_stamps.so")
 SLOTS = 256          # kStampU64 (mpcqp.hip)
 PHASES = ["inputs, model, Ya/Yb, g", "H tile", "sweep H^-1", "active set", "KKT check", "-"]
+# the first phase between its sub-stamps (slots 9..11; wave 0's clock)
+SUBPHASES = ["stage inputs", "stance list", "model (to Ya/Yb)", "g, barrier"]
 # section k runs from SEC(k) to the next SEC (mpcqp_solve.h); lanes 3, 4, 14, 15 are counters
 SECTIONS = {0: "argmin p + a_p rows", 1: "combo + LDS store", 2: "zs = A z (LDS)", 5: "add: q, 1/s, loads, coefs",
             6: "drop: R_l, H R_l, R H R_l", 8: "pair candidate", 9: "barrier", 10: "pair-step test",
@@ -76,6 +79,14 @@ def main():
     print(f"B={B} N={N}  iterations mean {iters.mean():.1f} max {iters.max()}")
     for k, name in enumerate(PHASES):
         print(f"  {name:26s} median {np.median(dts[:, k]):9.0f}  max {dts[:, k].max():9.0f} cycles")
+    sub = slots[:, 9:12]
+    if sub.min() > 0:   # the first phase's sub-stamps (SUBSTAMP, mpcqp_solve.h)
+        edges = np.concatenate([ts[:, :1], sub, ts[:, 1:2]], axis=1)
+        for k, name in enumerate(SUBPHASES):
+            v = edges[:, k + 1] - edges[:, k]
+            print(f"    {name:24s} median {np.median(v):9.0f}  max {v.max():9.0f} cycles")
+    setup = ts[:, 3] - ts[:, 0]
+    print(f"  {'setup (first three)':26s} median {np.median(setup):9.0f}  max {setup.max():9.0f} cycles")
     tot = ts[:, 6] - ts[:, 0]
     print(f"  {'total':26s} median {np.median(tot):9.0f}  max {tot.max():9.0f}")
     rt = slots[:, 7:9]
