@@ -233,6 +233,72 @@ int mpcqp_set_planner(mpcqp_ctx* ctx, double dt_control, double gravity, double 
 int mpcqp_stance_torques(mpcqp_ctx* ctx, int32_t batch, const float* jac, const float* stance,
                          int32_t stance_stride, const float* u0, float* tau, void* stream);
 
+/* ---- the leg controller on the device: all 12 joint torques per control iteration ----
+ *
+ * mpcqp_leg_torques replaces, batched over robots x legs, the rest of the loop body of
+ * scripts/isaacgym_a1.py:137-162:
+ *   Gait.set_iteration / get_swing_state                            gait.py:76-79,102-121
+ *   SwingFootTrajectoryGenerator.set_foot_placement  swing_foot_trajectory_generator.py:84-129
+ *   generate_swing_foot_trajectory / compute_traj_swingfoot         :38-82
+ *   LegController.update, swing and stance branch                   leg_controller.py:75-90
+ * Call it every control iteration.  One launch, no allocation, synchronisation or host
+ * read: it can be captured into a HIP graph (tick lives on the device, so a replay sees
+ * fresh counters).  A leg swings while its swing state is > 0 and is in stance otherwise;
+ * the decision is taken in integer arithmetic on tick % (iterations_between_mpc * period).
+ * A swing offset past the period wraps per leg, and a leg whose stance fills the period
+ * never swings (deviations).
+ *
+ *   flags        0 (reserved)
+ *   tick         [B]     int32: each robot's control-iteration counter (iter_counter,
+ *                        isaacgym_a1.py:137)
+ *   iterations_between_mpc   linear_mpc_configs.py:7 (20); >= 1
+ *   quat, pos, vel, rot, vel_body_des, yaw_rate_des, gait   as for mpcqp_plan (gait required)
+ *   thighs       [B][4][3]  hip positions, base frame (robot_data.base_pos_base_thighs)
+ *   pos_feet     [B][4][3]  foot positions, world frame (robot_data.pos_feet)
+ *   foot_pos_base, foot_vel_base [B][4][3]  foot position / velocity relative to the base,
+ *                        base frame (robot_data.base_pos_base_feet, base_vel_base_feet)
+ *   jac          [B][4][3][3]  as for mpcqp_stance_torques
+ *   u0           [B][12]  contact forces (mpc.py:99)
+ *   swing_mem    [B][MPCQP_SWING_STRIDE] float64 in/out, 16-byte aligned: per leg
+ *                        armed (1 while a swing is under way), remaining swing time,
+ *                        footpos_init[3], footpos_final[3] (world); all-zero = first swing
+ *                        (swing_foot_trajectory_generator.py:19-24).  Written only for legs
+ *                        in swing.
+ *   tau          [B][12]  out: every entry -- swing legs Jv^T [Kp (R p_des - R p_foot) +
+ *                        Kd (R v_des - R v_foot)], stance legs Jv^T (-f) (bitwise what
+ *                        mpcqp_stance_torques writes)
+ *   swing_state  [B][4]   out (nullable): gait.py:102-121, 0 = stance
+ *   pos_target, vel_target [B][4][3]  out (nullable): swing-foot targets relative to the
+ *                        base, base frame (isaacgym_a1.py:147-160); 0 for stance legs
+ * dt_control and gravity are mpcqp_set_planner's. */
+#define MPCQP_SWING_STRIDE 32
+int mpcqp_leg_torques(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const int32_t* tick,
+                      int32_t iterations_between_mpc, const float* quat, const float* pos, const float* vel,
+                      const float* rot, const double* vel_body_des, const double* yaw_rate_des,
+                      const int32_t* gait, const float* thighs, const float* pos_feet,
+                      const float* foot_pos_base, const float* foot_vel_base, const float* jac, const float* u0,
+                      double* swing_mem, float* tau, float* swing_state, float* pos_target, float* vel_target,
+                      void* stream);
+
+/* The same, reading Isaac Gym's actor root-state tensor in place (see
+ * mpcqp_plan_root_states; isaacgym_a1.py:119-128). */
+int mpcqp_leg_torques_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const int32_t* tick,
+                                  int32_t iterations_between_mpc, const float* root_states,
+                                  const double* vel_body_des, const double* yaw_rate_des, const int32_t* gait,
+                                  const float* thighs, const float* pos_feet, const float* foot_pos_base,
+                                  const float* foot_vel_base, const float* jac, const float* u0,
+                                  double* swing_mem, float* tau, float* swing_state, float* pos_target,
+                                  float* vel_target, void* stream);
+
+/* Swing constants: the apex height of the swing curve, an absolute world z
+ * (RobotConfig.swing_height, robot_configs.py:54, 0.1), the PD gains Kp / Kd [3][3]
+ * row-major HOST doubles (robot_configs.py:55-56, A1Config: 700 I and 20 I; NULL keeps the
+ * current matrix), the foothold's world z (swing_foot_trajectory_generator.py:120, -0.0255)
+ * and the gain of its velocity-error term (:116, 0.03).  A non-finite value returns
+ * MPCQP_ERR_ARG and leaves the previous constants in force. */
+int mpcqp_set_swing(mpcqp_ctx* ctx, double swing_height, const double* Kp, const double* Kd,
+                    double touchdown_z, double vel_gain);
+
 int mpcqp_destroy(mpcqp_ctx* ctx);
 
 const char* mpcqp_last_error(const mpcqp_ctx* ctx);

@@ -346,6 +346,7 @@ __device__ __forceinline__ int wave_argmin_f32(double v, double& vmin_out) {
 #include "mpcqp_solve.h"
 #include "mpcqp_ipm.h"
 #include "mpcqp_plan.h"
+#include "mpcqp_swing.h"
 
 // Workgroups are dealt round-robin over the 8 XCDs (block bid runs on XCD bid % 8,
 // MI355X_MICROARCH.md "Workgroup dispatch"; speed only, never correctness).  Block bid
@@ -674,6 +675,11 @@ struct mpcqp_ctx {
   double dt_control;  // planner constants (mpcqp_set_planner)
   double gravity;
   double max_pos_error;
+  double swing_height;   // swing constants (mpcqp_set_swing)
+  double touchdown_z;
+  double vel_gain;
+  double kp_swing[9];
+  double kd_swing[9];
   std::string err;
 };
 
@@ -824,6 +830,13 @@ int mpcqp_create(const mpcqp_params* p, int32_t device, mpcqp_ctx** out) {
   for (int i = 0; i < 12 * 12; ++i) ctx->r_full[i] = (i % 13 == 0) ? p->r_diag[i / 13] : 0.0;
   ctx->dt_control = 0.001;    // linear_mpc_configs.py:6
   ctx->gravity = 9.81;        // linear_mpc_configs.py:13
+  ctx->swing_height = 0.1;    // robot_configs.py:54
+  ctx->touchdown_z = -0.0255; // swing_foot_trajectory_generator.py:120
+  ctx->vel_gain = 0.03;       // swing_foot_trajectory_generator.py:116
+  for (int i = 0; i < 9; ++i) {
+    ctx->kp_swing[i] = i % 4 == 0 ? 700.0 : 0.0;   // robot_configs.py:55-56
+    ctx->kd_swing[i] = i % 4 == 0 ? 20.0 : 0.0;
+  }
   ctx->max_pos_error = 0.1;   // mpc.py:121
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->ncu = prop.multiProcessorCount;
@@ -1178,6 +1191,82 @@ int mpcqp_stance_torques(mpcqp_ctx* ctx, int32_t batch, const float* jac, const 
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("torque launch: ") + hipGetErrorString(e));
   return MPCQP_OK;
+}
+
+int mpcqp_set_swing(mpcqp_ctx* ctx, double swing_height, const double* Kp, const double* Kd, double touchdown_z,
+                    double vel_gain) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  bool finite = std::isfinite(swing_height) && std::isfinite(touchdown_z) && std::isfinite(vel_gain);
+  for (int i = 0; i < 9 && finite; ++i)
+    finite = (!Kp || std::isfinite(Kp[i])) && (!Kd || std::isfinite(Kd[i]));
+  if (!finite) return set_err(ctx, MPCQP_ERR_ARG, "non-finite swing constant");
+  ctx->swing_height = swing_height;
+  ctx->touchdown_z = touchdown_z;
+  ctx->vel_gain = vel_gain;
+  if (Kp) memcpy(ctx->kp_swing, Kp, sizeof(ctx->kp_swing));
+  if (Kd) memcpy(ctx->kd_swing, Kd, sizeof(ctx->kd_swing));
+  return MPCQP_OK;
+}
+
+static int launch_leg_torques(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int root_layout, const int32_t* tick,
+                              int32_t iterations_between_mpc, const float* quat, const float* pos, const float* vel,
+                              const float* rot, const double* vel_body_des, const double* yaw_rate_des,
+                              const int32_t* gait, const float* thighs, const float* pos_feet,
+                              const float* foot_pos_base, const float* foot_vel_base, const float* jac,
+                              const float* u0, double* swing_mem, float* tau, float* swing_state, float* pos_target,
+                              float* vel_target, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "batch < 0");
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown leg-torque flags");
+  if (iterations_between_mpc < 1) return set_err(ctx, MPCQP_ERR_ARG, "iterations_between_mpc < 1");
+  if (batch == 0) return MPCQP_OK;
+  if (!tick || !quat || (!root_layout && (!pos || !vel)) || !vel_body_des || !yaw_rate_des || !gait || !thighs ||
+      !pos_feet || !foot_pos_base || !foot_vel_base || !jac || !u0 || !swing_mem || !tau)
+    return set_err(ctx, MPCQP_ERR_ARG, "null leg-torque input/output pointer");
+  if ((uintptr_t)swing_mem & 15) return set_err(ctx, MPCQP_ERR_ARG, "swing_mem is not 16-byte aligned");
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  SwingParams sp;
+  sp.ibm = iterations_between_mpc;
+  sp.root_layout = root_layout;
+  sp.dt_control = ctx->dt_control;
+  sp.gravity = ctx->gravity;
+  sp.swing_height = ctx->swing_height;
+  sp.touchdown_z = ctx->touchdown_z;
+  sp.vel_gain = ctx->vel_gain;
+  memcpy(sp.Kp, ctx->kp_swing, sizeof(sp.Kp));
+  memcpy(sp.Kd, ctx->kd_swing, sizeof(sp.Kd));
+  hipLaunchKernelGGL(mpcqp_leg_torque_kernel, dim3((batch + kSwingRobots - 1) / kSwingRobots), dim3(kSwingThreads),
+                     0, (hipStream_t)stream, sp, (int)batch, tick, quat, pos, vel, rot, vel_body_des, yaw_rate_des,
+                     gait, thighs, pos_feet, foot_pos_base, foot_vel_base, jac, u0, swing_mem, tau, swing_state,
+                     pos_target, vel_target);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    return set_err(ctx, MPCQP_ERR_HIP, std::string("leg-torque launch: ") + hipGetErrorString(e));
+  return MPCQP_OK;
+}
+
+int mpcqp_leg_torques(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const int32_t* tick,
+                      int32_t iterations_between_mpc, const float* quat, const float* pos, const float* vel,
+                      const float* rot, const double* vel_body_des, const double* yaw_rate_des, const int32_t* gait,
+                      const float* thighs, const float* pos_feet, const float* foot_pos_base,
+                      const float* foot_vel_base, const float* jac, const float* u0, double* swing_mem, float* tau,
+                      float* swing_state, float* pos_target, float* vel_target, void* stream) {
+  return launch_leg_torques(ctx, batch, flags, 0, tick, iterations_between_mpc, quat, pos, vel, rot, vel_body_des,
+                            yaw_rate_des, gait, thighs, pos_feet, foot_pos_base, foot_vel_base, jac, u0, swing_mem,
+                            tau, swing_state, pos_target, vel_target, stream);
+}
+
+int mpcqp_leg_torques_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const int32_t* tick,
+                                  int32_t iterations_between_mpc, const float* root_states,
+                                  const double* vel_body_des, const double* yaw_rate_des, const int32_t* gait,
+                                  const float* thighs, const float* pos_feet, const float* foot_pos_base,
+                                  const float* foot_vel_base, const float* jac, const float* u0, double* swing_mem,
+                                  float* tau, float* swing_state, float* pos_target, float* vel_target,
+                                  void* stream) {
+  return launch_leg_torques(ctx, batch, flags, 1, tick, iterations_between_mpc, root_states, nullptr, nullptr,
+                            nullptr, vel_body_des, yaw_rate_des, gait, thighs, pos_feet, foot_pos_base,
+                            foot_vel_base, jac, u0, swing_mem, tau, swing_state, pos_target, vel_target, stream);
 }
 
 int mpcqp_destroy(mpcqp_ctx* ctx) {

@@ -44,6 +44,22 @@ struct PlanSeed {
   int period, ih0, off[4], dur[4];
 };
 
+// quat2matrix (kinematics.py:51-71) on a float32 quaternion (w, x, y, z), in NumPy's
+// float32 scalar arithmetic: every product and sum rounds (R row-major)
+__device__ inline void plan_quat2matrix(float qw, float qx, float qy, float qz, float (&R)[9]) {
+#pragma clang fp contract(off)
+  const float ww = (qw * qw), xx = (qx * qx), yy = (qy * qy), zz = (qz * qz);
+  R[0] = (((ww + xx) - yy) - zz);
+  R[1] = 2.f * ((qx * qy) - (qw * qz));
+  R[2] = 2.f * ((qw * qy) + (qx * qz));
+  R[3] = 2.f * ((qw * qz) + (qx * qy));
+  R[4] = (((ww - xx) + yy) - zz);
+  R[5] = 2.f * ((qy * qz) - (qw * qx));
+  R[6] = 2.f * ((qx * qz) - (qw * qy));
+  R[7] = 2.f * ((qw * qx) + (qy * qz));
+  R[8] = (((ww - xx) - yy) + zz);
+}
+
 __global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
     PlanParams pp, int B, const float* __restrict__ quat, const float* __restrict__ pos,
     const float* __restrict__ omega, const float* __restrict__ vel, const float* __restrict__ rot,
@@ -114,17 +130,7 @@ __global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
 #pragma unroll
       for (int k = 0; k < 9; ++k) R[k] = rot[9 * b + k];
     } else {
-      const float ww = (qw * qw), xx = (qx * qx), yy = (qy * qy),
-                  zz = (qz * qz);
-      R[0] = (((ww + xx) - yy) - zz);
-      R[1] = 2.f * ((qx * qy) - (qw * qz));
-      R[2] = 2.f * ((qw * qy) + (qx * qz));
-      R[3] = 2.f * ((qw * qz) + (qx * qy));
-      R[4] = (((ww - xx) + yy) - zz);
-      R[5] = 2.f * ((qy * qz) - (qw * qx));
-      R[6] = 2.f * ((qx * qz) - (qw * qy));
-      R[7] = 2.f * ((qw * qx) + (qy * qz));
-      R[8] = (((ww - xx) - yy) + zz);
+      plan_quat2matrix(qw, qx, qy, qz, R);
     }
     // the body-frame command is float64 (a Python list / float64 array in the scripts)
     double vdes[3];

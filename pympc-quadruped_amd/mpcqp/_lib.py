@@ -41,6 +41,9 @@ EXPORTED_SYMBOLS = (
     "mpcqp_plan_root_states",
     "mpcqp_set_planner",
     "mpcqp_stance_torques",
+    "mpcqp_leg_torques",
+    "mpcqp_leg_torques_root_states",
+    "mpcqp_set_swing",
 )
 ABI_VERSION = 6
 WARM_BYTES = 128     # MPCQP_WARM_BYTES: warm-start memory per robot
@@ -48,6 +51,7 @@ PLAN_STRIDE = 8     # MPCQP_PLAN_STRIDE: float64 planner state per robot
 GAIT_STRIDE = 9     # MPCQP_GAIT_STRIDE: period, offsets[4], durations[4]
 PLAN_REFERENCE = 1      # MPCQP_PLAN_REFERENCE: build X_ref (+ gait table) this tick
 PLAN_NO_INTEGRATE = 2   # MPCQP_PLAN_NO_INTEGRATE: skip the desired-pose integrators
+SWING_STRIDE = 32   # MPCQP_SWING_STRIDE: float64 swing-generator state per robot (8 per leg)
 
 
 class MpcqpParams(ctypes.Structure):
@@ -108,6 +112,12 @@ def load():
     lib.mpcqp_set_planner.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
     lib.mpcqp_stance_torques.restype = ctypes.c_int
     lib.mpcqp_stance_torques.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
+    lib.mpcqp_leg_torques.restype = ctypes.c_int
+    lib.mpcqp_leg_torques.argtypes = [vp, i32, i32, vp, i32] + [vp] * 18 + [vp]
+    lib.mpcqp_leg_torques_root_states.restype = ctypes.c_int
+    lib.mpcqp_leg_torques_root_states.argtypes = [vp, i32, i32, vp, i32] + [vp] * 15 + [vp]
+    lib.mpcqp_set_swing.restype = ctypes.c_int
+    lib.mpcqp_set_swing.argtypes = [vp, ctypes.c_double, vp, vp, ctypes.c_double, ctypes.c_double]
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise MpcqpError("libmpcqp ABI version mismatch")
     _lib = lib

@@ -1,26 +1,32 @@
 """Batched control tick on the device: the loop body the reference runs per robot.
 
 ``BatchedController`` is B copies of the reference's per-robot objects -- one
-``Gait``, one ``ModelPredictiveController`` and the stance branch of one
-``LegController`` -- advanced together, so a whole fleet's control iteration is
-three HIP launches with every intermediate resident in HBM:
+``Gait``, one ``ModelPredictiveController``, four ``SwingFootTrajectoryGenerator``s and
+one ``LegController`` -- advanced together, so a whole fleet's control iteration is
+three HIP launches on an MPC tick and two (plan, leg_torques) on the others, with
+every intermediate resident in HBM:
 
   mpcqp_plan            Gait.set_iteration / get_gait_table          gait.py:76-100
                         ModelPredictiveController.update_robot_state mpc.py:55-79
                         update_mpc_if_needed integrators, X_ref      mpc.py:81-170
   mpcqp_solve           _solve_mpc on MPC ticks                      mpc.py:262-290
-  mpcqp_stance_torques  LegController stance branch                  leg_controller.py:86-89
+  mpcqp_leg_torques     Gait.get_swing_state                         gait.py:102-121
+                        set_foot_placement, compute_traj_swingfoot
+                                            swing_foot_trajectory_generator.py:38-129
+                        LegController.update, both branches          leg_controller.py:75-90
+  mpcqp_stance_torques  LegController stance branch alone            leg_controller.py:86-89
 
-The per-robot Python loop it replaces is scripts/isaacgym_a1.py:117-151 (which
-copies every robot's root state to the host, ``.cpu().numpy()``); ``tick`` takes
-the simulator's root-state tensor as it lies on the device.
+The per-robot Python loop it replaces is scripts/isaacgym_a1.py:117-162 (which
+copies every robot's root state to the host, ``.cpu().numpy()``); ``tick`` and
+``leg_torques`` take the simulator's root-state tensor as it lies on the device
+(SURVEY §8 f3).  ``torques`` remains for callers that run their own swing controller.
 """
 import numpy as np
 import torch
 
-from ._lib import PLAN_REFERENCE, PLAN_STRIDE
+from ._lib import PLAN_REFERENCE, PLAN_STRIDE, SWING_STRIDE
 from .engine import LinearMpc
-from .params import DT_MPC, Q_DIAG, R_DIAG, ROBOT_PRESETS, gait_record
+from .params import DT_MPC, Q_DIAG, R_DIAG, ROBOT_PRESETS, SWING_PRESETS, gait_record
 
 
 class BatchedController:
@@ -34,11 +40,15 @@ class BatchedController:
       dt_control: linear_mpc_configs.py:6 (0.001)
       height:   desired CoM height(s) (robot_configs.py:23,42); default from the preset
       warm_start: remember each robot's active set between MPC ticks (LinearMpc.set_warm_start)
+      swing:    swing constants for ``leg_torques``: a dict with any of swing_height, Kp, Kd,
+                touchdown_z, vel_gain (LinearMpc.set_swing).  Default: the robot preset's or the
+                RobotConfig class's swing_height / Kp_swing / Kd_swing (robot_configs.py:35-37,
+                54-56); a packed record carries none and gets the engine's defaults
     """
 
     def __init__(self, batch, horizon=16, robot="aliengo", gait="trot10", iterations_between_mpc=20,
                  dt_control=0.001, gravity=9.81, height=None, dt=DT_MPC, Q=Q_DIAG, R=R_DIAG,
-                 device="cuda:0", max_iter=0, max_stance=0, warm_start=True):
+                 device="cuda:0", max_iter=0, max_stance=0, warm_start=True, swing=None):
         self.B = int(batch)
         self.N = int(horizon)
         self.iterations_between_mpc = int(iterations_between_mpc)
@@ -48,6 +58,14 @@ class BatchedController:
         self.engine.set_planner(dt_control=dt_control, gravity=gravity)
         if warm_start:   # the fleet is solved tick after tick: remember each robot's active set
             self.engine.set_warm_start(int(batch))
+        if swing is None:
+            if isinstance(robot, str):
+                sw = SWING_PRESETS[robot]
+                swing = dict(swing_height=sw["swing_height"], Kp=sw["kp"], Kd=sw["kd"])
+            elif hasattr(robot, "Kp_swing"):
+                swing = dict(swing_height=robot.swing_height, Kp=robot.Kp_swing, Kd=robot.Kd_swing)
+        if swing:
+            self.engine.set_swing(**swing)
         dev = self.engine.device
         self.device = dev
         B, N = self.B, self.N
@@ -82,13 +100,23 @@ class BatchedController:
         self.status = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.iterations = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.iteration = torch.zeros((B,), dtype=torch.int32, device=dev)
+        # leg_torques: the swing generators' state, each robot's control-iteration counter
+        # and the optional outputs
+        self.swing_mem = torch.zeros((B, SWING_STRIDE), dtype=torch.float64, device=dev)
+        self.tick_count = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.swing_state = torch.zeros((B, 4), **f32)
+        self.pos_target = torch.zeros((B, 4, 3), **f32)
+        self.vel_target = torch.zeros((B, 4, 3), **f32)
 
     def reset(self, robots=None):
-        """First-run semantics again (mpc.py:56-60,84-87) for all or some robots."""
+        """First-run semantics again (mpc.py:56-60,84-87; first swing,
+        swing_foot_trajectory_generator.py:19-24) for all or some robots."""
         if robots is None:
             self.plan_state.zero_()
+            self.swing_mem.zero_()
         else:
             self.plan_state[robots] = 0.0
+            self.swing_mem[robots] = 0.0
 
     def _cmd(self, v, shape):
         t = torch.as_tensor(v, dtype=torch.float64)
@@ -137,4 +165,37 @@ class BatchedController:
         j = jac.to(self.device, torch.float32).contiguous()
         s = stance.to(self.device, torch.float32).contiguous()
         self.engine.stance_torques(j, s, self.u0, self.tau, stance_stride=s.shape[-1])
+        return self.tau
+
+    def leg_torques(self, iter_counter, vel_body_des, yaw_rate_des, thighs, pos_feet, foot_pos_base, foot_vel_base,
+                    jac, root_states=None, quat=None, pos=None, vel=None, rot=None):
+        """All 12 joint torques of every robot into self.tau: the rest of the loop body
+        after ``tick`` (isaacgym_a1.py:137-162) in one launch, with no host read.
+
+        ``iter_counter``: the control-iteration counter of ``tick``; an int is written to
+        the device counters ``self.tick_count`` (one fill), None leaves them to the caller
+        (per-robot offsets, or a captured graph that advances them on the device).
+        thighs [B,4,3] hip positions in the base frame, pos_feet [B,4,3] feet in the world
+        frame, foot_pos_base / foot_vel_base [B,4,3] feet relative to the base in the base
+        frame, jac [B,4,3,3] as for ``torques``.  Legs in swing (self.swing_state > 0) get
+        the swing PD law on the generated targets (self.pos_target, self.vel_target),
+        the others Jv^T (-f) from self.u0."""
+        B = self.B
+        if iter_counter is not None:
+            self.tick_count.fill_(int(iter_counter))
+        vb = self._cmd(vel_body_des, (B, 3))
+        yr = self._cmd(yaw_rate_des, (B,))
+        th, pf, fp, fv, j = [t.to(self.device, torch.float32).contiguous()
+                             for t in (thighs, pos_feet, foot_pos_base, foot_vel_base, jac)]
+        kw = dict(swing_state=self.swing_state, pos_target=self.pos_target, vel_target=self.vel_target)
+        if root_states is not None:
+            rs = root_states if root_states.dtype == torch.float32 and root_states.is_contiguous() \
+                else root_states.to(torch.float32).contiguous()
+            kw["root_states"] = rs
+        else:
+            c = [t.to(self.device, torch.float32).contiguous() for t in (quat, pos, vel)]
+            kw.update(quat=c[0], pos=c[1], vel=c[2],
+                      rot=rot.to(self.device, torch.float32).contiguous() if rot is not None else None)
+        self.engine.leg_torques(self.tick_count, self.iterations_between_mpc, vb, yr, self.gait, th, pf, fp, fv, j,
+                                self.u0, self.swing_mem, self.tau, **kw)
         return self.tau

@@ -321,3 +321,55 @@ class LinearMpc:
         code = self.lib.mpcqp_stance_torques(self._ctx, B, _ptr(jac), _ptr(stance), int(stance_stride), _ptr(u0),
                                              _ptr(tau), ctypes.c_void_p(stream.cuda_stream))
         _lib.check(self._ctx, code, "mpcqp_stance_torques")
+
+    def set_swing(self, swing_height=0.1, Kp=None, Kd=None, touchdown_z=-0.0255, vel_gain=0.03):
+        """Swing constants (include/mpcqp.h mpcqp_set_swing): the curve's apex height (a world
+        z, robot_configs.py:54), the PD gains -- a scalar, a diagonal or a 3 x 3 matrix, None
+        keeps the current one (robot_configs.py:55-56) -- the foothold's world z and the gain
+        of its velocity-error term (swing_foot_trajectory_generator.py:116,120).  Like
+        set_planner, every call sets all three scalars (an omitted one returns to its default);
+        launches already issued keep the constants they were issued with."""
+        def gain(k):
+            if k is None:
+                return None
+            k = np.asarray(k, dtype=np.float64)
+            if k.ndim == 0:
+                k = k * np.eye(3)
+            elif k.ndim == 1:
+                k = np.diag(k)
+            if k.shape != (3, 3):
+                raise ValueError("a swing gain is a scalar, 3 diagonal entries or a 3 x 3 matrix")
+            return np.ascontiguousarray(k)
+        kp, kd = gain(Kp), gain(Kd)
+        code = self.lib.mpcqp_set_swing(self._ctx, float(swing_height), kp.ctypes.data if kp is not None else None,
+                                        kd.ctypes.data if kd is not None else None, float(touchdown_z),
+                                        float(vel_gain))
+        _lib.check(self._ctx, code, "mpcqp_set_swing")
+
+    def leg_torques(self, tick, iterations_between_mpc, vel_body_des, yaw_rate_des, gait, thighs, pos_feet,
+                    foot_pos_base, foot_vel_base, jac, u0, swing_mem, tau, quat=None, pos=None, vel=None, rot=None,
+                    root_states=None, swing_state=None, pos_target=None, vel_target=None, stream=None):
+        """All 12 joint torques of every robot for one control iteration (include/mpcqp.h
+        mpcqp_leg_torques; isaacgym_a1.py:137-162): swing state, foot placement, swing
+        trajectory, swing PD and stance torques in one launch.
+
+        Every argument is a preallocated contiguous device tensor: tick [B] / gait [B,9]
+        int32, vel_body_des [B,3] / yaw_rate_des [B] / swing_mem [B,SWING_STRIDE] float64,
+        the rest float32 (thighs, pos_feet, foot_pos_base, foot_vel_base [B,4,3], jac
+        [B,4,3,3], u0 / tau [B,12]).  ``root_states`` [B,13] (Isaac Gym layout) replaces
+        quat/pos/vel/rot.  swing_state [B,4], pos_target / vel_target [B,4,3] are optional
+        outputs."""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        B = int(tau.shape[0])
+        s = ctypes.c_void_p(stream.cuda_stream)
+        tail = (_ptr(vel_body_des), _ptr(yaw_rate_des), _ptr(gait), _ptr(thighs), _ptr(pos_feet),
+                _ptr(foot_pos_base), _ptr(foot_vel_base), _ptr(jac), _ptr(u0), _ptr(swing_mem), _ptr(tau),
+                _ptr(swing_state), _ptr(pos_target), _ptr(vel_target), s)
+        if root_states is not None:
+            code = self.lib.mpcqp_leg_torques_root_states(self._ctx, B, 0, _ptr(tick), int(iterations_between_mpc),
+                                                          _ptr(root_states), *tail)
+        else:
+            code = self.lib.mpcqp_leg_torques(self._ctx, B, 0, _ptr(tick), int(iterations_between_mpc), _ptr(quat),
+                                              _ptr(pos), _ptr(vel), _ptr(rot), *tail)
+        _lib.check(self._ctx, code, "mpcqp_leg_torques")

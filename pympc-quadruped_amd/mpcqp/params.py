@@ -37,6 +37,10 @@ ROBOT_PRESETS = {
                                 0.056579028, 2.5134e-05, 0.064713601, scale=10)),
 }
 
+# swing constants: swing_height, Kp_swing, Kd_swing (diagonal)   robot_configs.py:35-37,54-56
+SWING_PRESETS = {"aliengo": dict(swing_height=0.1, kp=200.0, kd=20.0),
+                 "a1": dict(swing_height=0.1, kp=700.0, kd=20.0)}
+
 # hip x offset, hip y + thigh y offset (a1.urdf:90,212,254; aliengo.urdf:99,254,297)
 HIP_OFFSETS = {"a1": (0.183, 0.047 + 0.08505), "aliengo": (0.2399, 0.051 + 0.083)}
 
