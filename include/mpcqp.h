@@ -299,6 +299,51 @@ int mpcqp_leg_torques_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, 
 int mpcqp_set_swing(mpcqp_ctx* ctx, double swing_height, const double* Kp, const double* Kd,
                     double touchdown_z, double vel_gain);
 
+/* ---- the leg kinematics on the device: every array the entry points above consume ----
+ *
+ * mpcqp_kinematics replaces, batched over robots x legs, RobotData.update
+ * (utils/robot_data.py:59-108) -- pinocchio.forwardKinematics / framesForwardKinematics
+ * (:91-92), computeFrameJacobian (:117-133) and the frame changes (:135-184) -- for the leg
+ * both shipped robots have: hip revolute about x, thigh and calf revolute about y, zero
+ * joint rpy (a1.urdf:211-310, aliengo.urdf:253-358).  Leg order FL, FR, RL, RR.  One launch,
+ * no allocation, synchronisation or host read.  Float64 arithmetic on the float32 inputs,
+ * each output rounded to float32 once.
+ *
+ *   flags        0 (reserved)
+ *   quat, pos, vel, omega, rot   as for mpcqp_plan: the free-flyer rotation Rq is Eigen's
+ *                        quaternion-to-matrix formula in float64 on quat as given (not
+ *                        normalised, robot_data.py:85-92); R_base is rot, or quat2matrix in
+ *                        float32 arithmetic when rot is NULL (:75)
+ *   q, qdot      [B][12]  joint angles / rates, three per leg (hip, thigh, calf)
+ *   geom         [B][MPCQP_KIN_STRIDE] float64: hip_x, hip_y, thigh_y, l_thigh, l_calf, 0, 0, 0
+ *                        (magnitudes; the leg's signs are applied here)
+ * Outputs, each nullable (a NULL output is not written):
+ *   feet         [B][4][3]  Rq p: feet relative to the base, world frame
+ *                        (robot_data.pos_base_feet, :101) -- the `feet` of mpcqp_solve
+ *   thighs       [B][4][3]  R_base^T Rq p_thigh (base_pos_base_thighs, :108)
+ *   pos_feet     [B][4][3]  pos + Rq p (pos_feet, :99)
+ *   foot_pos_base [B][4][3] R_base^T Rq p (base_pos_base_feet, :103)
+ *   foot_vel_base [B][4][3] R_base^T (Rq (vel + omega x p + J_b qdot) - vel)
+ *                        (base_vel_base_feet, :158-167: the reference multiplies Pinocchio's
+ *                        body-frame free-flyer columns by the world-frame vel / omega, and so
+ *                        does this; DESIGN.md, deviations)
+ *   jac          [B][4][3][3]  Rq J_b, the block Jv_feet[leg][:, 6 + 3 leg : 9 + 3 leg]
+ *                        (:117-133, LOCAL_WORLD_ALIGNED); as for mpcqp_stance_torques
+ * with p, p_thigh the foot and thigh-joint position in the base frame and J_b = dp/dq. */
+#define MPCQP_KIN_STRIDE 8
+int mpcqp_kinematics(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* quat, const float* pos,
+                     const float* vel, const float* omega, const float* rot, const float* q, const float* qdot,
+                     const double* geom, float* feet, float* thighs, float* pos_feet, float* foot_pos_base,
+                     float* foot_vel_base, float* jac, void* stream);
+
+/* The same, reading Isaac Gym's tensors in place: root_states [B][13] (see
+ * mpcqp_plan_root_states) and the dof-state tensor dof_states [B][12][2], (pos, vel) per
+ * DOF -- what isaacgym_a1.py:116,119-132 slices and copies to the host per robot. */
+int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* root_states,
+                                 const float* dof_states, const double* geom, float* feet, float* thighs,
+                                 float* pos_feet, float* foot_pos_base, float* foot_vel_base, float* jac,
+                                 void* stream);
+
 int mpcqp_destroy(mpcqp_ctx* ctx);
 
 const char* mpcqp_last_error(const mpcqp_ctx* ctx);

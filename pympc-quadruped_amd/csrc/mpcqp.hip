@@ -347,6 +347,8 @@ __device__ __forceinline__ int wave_argmin_f32(double v, double& vmin_out) {
 #include "mpcqp_ipm.h"
 #include "mpcqp_plan.h"
 #include "mpcqp_swing.h"
+#include "mpcqp_kinematics.h"
+static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 
 // Workgroups are dealt round-robin over the 8 XCDs (block bid runs on XCD bid % 8,
 // MI355X_MICROARCH.md "Workgroup dispatch"; speed only, never correctness).  Block bid
@@ -1267,6 +1269,46 @@ int mpcqp_leg_torques_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, 
   return launch_leg_torques(ctx, batch, flags, 1, tick, iterations_between_mpc, root_states, nullptr, nullptr,
                             nullptr, vel_body_des, yaw_rate_des, gait, thighs, pos_feet, foot_pos_base,
                             foot_vel_base, jac, u0, swing_mem, tau, swing_state, pos_target, vel_target, stream);
+}
+
+static int launch_kinematics(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int root_layout, const float* quat,
+                             const float* pos, const float* vel, const float* omega, const float* rot,
+                             const float* q, const float* qdot, const double* geom, float* feet, float* thighs,
+                             float* pos_feet, float* foot_pos_base, float* foot_vel_base, float* jac,
+                             void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "batch < 0");
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown kinematics flags");
+  if (batch == 0) return MPCQP_OK;
+  if (!quat || !q || !geom || (!root_layout && (!pos || !vel || !omega || !qdot)))
+    return set_err(ctx, MPCQP_ERR_ARG, "null kinematics input pointer");
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  KinParams kp;
+  kp.root_layout = root_layout;
+  hipLaunchKernelGGL(mpcqp_kinematics_kernel, dim3((batch + kKinRobots - 1) / kKinRobots), dim3(kKinThreads), 0,
+                     (hipStream_t)stream, kp, (int)batch, quat, pos, vel, omega, rot, q, qdot, geom, feet, thighs,
+                     pos_feet, foot_pos_base, foot_vel_base, jac);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    return set_err(ctx, MPCQP_ERR_HIP, std::string("kinematics launch: ") + hipGetErrorString(e));
+  return MPCQP_OK;
+}
+
+int mpcqp_kinematics(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* quat, const float* pos,
+                     const float* vel, const float* omega, const float* rot, const float* q, const float* qdot,
+                     const double* geom, float* feet, float* thighs, float* pos_feet, float* foot_pos_base,
+                     float* foot_vel_base, float* jac, void* stream) {
+  return launch_kinematics(ctx, batch, flags, 0, quat, pos, vel, omega, rot, q, qdot, geom, feet, thighs, pos_feet,
+                           foot_pos_base, foot_vel_base, jac, stream);
+}
+
+int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* root_states,
+                                 const float* dof_states, const double* geom, float* feet, float* thighs,
+                                 float* pos_feet, float* foot_pos_base, float* foot_vel_base, float* jac,
+                                 void* stream) {
+  return launch_kinematics(ctx, batch, flags, 1, root_states, nullptr, nullptr, nullptr, nullptr, dof_states,
+                           nullptr, geom, feet, thighs, pos_feet, foot_pos_base, foot_vel_base, jac, stream);
 }
 
 int mpcqp_destroy(mpcqp_ctx* ctx) {

@@ -3,11 +3,12 @@
 Drop-in for the formulate-and-solve hot path of yinghansun/pympc-quadruped
 (``ModelPredictiveController._solve_mpc``, linear_mpc/mpc.py:262-290).
 """
-from .params import (DT_MPC, GAITS, GRAVITY, MU, Q_DIAG, R_DIAG, ROBOT_PRESETS, ROBOT_STRIDE,
-                     pack_robot, robot_from_config)
+from .params import (DT_MPC, GAITS, GRAVITY, LEG_GEOMETRY, MU, Q_DIAG, R_DIAG, ROBOT_PRESETS, ROBOT_STRIDE,
+                     leg_geometry_from_urdf, pack_leg_geometry, pack_robot, robot_from_config)
 
-__all__ = ["LinearMpc", "SolveResult", "DT_MPC", "GAITS", "GRAVITY", "MU", "Q_DIAG", "R_DIAG",
-           "ROBOT_PRESETS", "ROBOT_STRIDE", "pack_robot", "robot_from_config"]
+__all__ = ["LinearMpc", "SolveResult", "DT_MPC", "GAITS", "GRAVITY", "LEG_GEOMETRY", "MU", "Q_DIAG", "R_DIAG",
+           "ROBOT_PRESETS", "ROBOT_STRIDE", "leg_geometry_from_urdf", "pack_leg_geometry", "pack_robot",
+           "robot_from_config"]
 
 
 def __getattr__(name):

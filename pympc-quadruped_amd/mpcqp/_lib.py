@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = (
     "mpcqp_leg_torques",
     "mpcqp_leg_torques_root_states",
     "mpcqp_set_swing",
+    "mpcqp_kinematics",
+    "mpcqp_kinematics_root_states",
 )
 ABI_VERSION = 6
 WARM_BYTES = 128     # MPCQP_WARM_BYTES: warm-start memory per robot
@@ -52,6 +54,7 @@ GAIT_STRIDE = 9     # MPCQP_GAIT_STRIDE: period, offsets[4], durations[4]
 PLAN_REFERENCE = 1      # MPCQP_PLAN_REFERENCE: build X_ref (+ gait table) this tick
 PLAN_NO_INTEGRATE = 2   # MPCQP_PLAN_NO_INTEGRATE: skip the desired-pose integrators
 SWING_STRIDE = 32   # MPCQP_SWING_STRIDE: float64 swing-generator state per robot (8 per leg)
+KIN_STRIDE = 8      # MPCQP_KIN_STRIDE: float64 leg geometry per robot (5 used)
 
 
 class MpcqpParams(ctypes.Structure):
@@ -118,6 +121,10 @@ def load():
     lib.mpcqp_leg_torques_root_states.argtypes = [vp, i32, i32, vp, i32] + [vp] * 15 + [vp]
     lib.mpcqp_set_swing.restype = ctypes.c_int
     lib.mpcqp_set_swing.argtypes = [vp, ctypes.c_double, vp, vp, ctypes.c_double, ctypes.c_double]
+    lib.mpcqp_kinematics.restype = ctypes.c_int
+    lib.mpcqp_kinematics.argtypes = [vp, i32, i32] + [vp] * 14 + [vp]
+    lib.mpcqp_kinematics_root_states.restype = ctypes.c_int
+    lib.mpcqp_kinematics_root_states.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise MpcqpError("libmpcqp ABI version mismatch")
     _lib = lib

@@ -3,9 +3,10 @@
 ``BatchedController`` is B copies of the reference's per-robot objects -- one
 ``Gait``, one ``ModelPredictiveController``, four ``SwingFootTrajectoryGenerator``s and
 one ``LegController`` -- advanced together, so a whole fleet's control iteration is
-three HIP launches on an MPC tick and two (plan, leg_torques) on the others, with
-every intermediate resident in HBM:
+four HIP launches on an MPC tick and three (kinematics, plan, leg_torques) on the
+others, with every intermediate resident in HBM:
 
+  mpcqp_kinematics      RobotData.update                             robot_data.py:59-108
   mpcqp_plan            Gait.set_iteration / get_gait_table          gait.py:76-100
                         ModelPredictiveController.update_robot_state mpc.py:55-79
                         update_mpc_if_needed integrators, X_ref      mpc.py:81-170
@@ -19,14 +20,17 @@ every intermediate resident in HBM:
 The per-robot Python loop it replaces is scripts/isaacgym_a1.py:117-162 (which
 copies every robot's root state to the host, ``.cpu().numpy()``); ``tick`` and
 ``leg_torques`` take the simulator's root-state tensor as it lies on the device
-(SURVEY §8 f3).  ``torques`` remains for callers that run their own swing controller.
+(SURVEY §8 f3).  ``step`` is the whole loop body on the simulator's two state tensors,
+with nothing computed by the caller; ``tick`` and ``leg_torques`` remain for callers with
+kinematics of their own, ``torques`` for callers that run their own swing controller.
 """
 import numpy as np
 import torch
 
 from ._lib import PLAN_REFERENCE, PLAN_STRIDE, SWING_STRIDE
 from .engine import LinearMpc
-from .params import DT_MPC, Q_DIAG, R_DIAG, ROBOT_PRESETS, SWING_PRESETS, gait_record
+from .params import (DT_MPC, LEG_GEOMETRY, Q_DIAG, R_DIAG, ROBOT_PRESETS, SWING_PRESETS, gait_record,
+                     pack_leg_geometry)
 
 
 class BatchedController:
@@ -44,11 +48,15 @@ class BatchedController:
                 touchdown_z, vel_gain (LinearMpc.set_swing).  Default: the robot preset's or the
                 RobotConfig class's swing_height / Kp_swing / Kd_swing (robot_configs.py:35-37,
                 54-56); a packed record carries none and gets the engine's defaults
+      geometry: leg geometry for ``step``: a LEG_GEOMETRY key, (hip_x, hip_y, thigh_y, l_thigh,
+                l_calf) or a [B,5] array for a mixed fleet (params.leg_geometry_from_urdf reads
+                one from a URDF).  Default: the robot preset's; without a preset name and
+                without geometry, ``step`` raises
     """
 
     def __init__(self, batch, horizon=16, robot="aliengo", gait="trot10", iterations_between_mpc=20,
                  dt_control=0.001, gravity=9.81, height=None, dt=DT_MPC, Q=Q_DIAG, R=R_DIAG,
-                 device="cuda:0", max_iter=0, max_stance=0, warm_start=True, swing=None):
+                 device="cuda:0", max_iter=0, max_stance=0, warm_start=True, swing=None, geometry=None):
         self.B = int(batch)
         self.N = int(horizon)
         self.iterations_between_mpc = int(iterations_between_mpc)
@@ -107,6 +115,16 @@ class BatchedController:
         self.swing_state = torch.zeros((B, 4), **f32)
         self.pos_target = torch.zeros((B, 4, 3), **f32)
         self.vel_target = torch.zeros((B, 4, 3), **f32)
+        # step: the leg geometry and the six outputs of the kinematics
+        if geometry is None and isinstance(robot, str) and robot in LEG_GEOMETRY:
+            geometry = robot
+        self.geometry = None if geometry is None else torch.as_tensor(pack_leg_geometry(geometry, B)).to(dev)
+        self.feet = torch.zeros((B, 4, 3), **f32)
+        self.thighs = torch.zeros((B, 4, 3), **f32)
+        self.pos_feet = torch.zeros((B, 4, 3), **f32)
+        self.foot_pos_base = torch.zeros((B, 4, 3), **f32)
+        self.foot_vel_base = torch.zeros((B, 4, 3), **f32)
+        self.jac = torch.zeros((B, 4, 3, 3), **f32)
 
     def reset(self, robots=None):
         """First-run semantics again (mpc.py:56-60,84-87; first swing,
@@ -199,3 +217,30 @@ class BatchedController:
         self.engine.leg_torques(self.tick_count, self.iterations_between_mpc, vb, yr, self.gait, th, pf, fp, fv, j,
                                 self.u0, self.swing_mem, self.tau, **kw)
         return self.tau
+
+    def kinematics(self, root_states, dof_states):
+        """RobotData.update (robot_data.py:59-108) for every robot in one launch, from the
+        simulator's actor root states [B,13] and dof states [B,12,2] (or [B*12,2], as Isaac
+        Gym hands them out) into self.feet, thighs, pos_feet, foot_pos_base, foot_vel_base
+        and jac."""
+        if self.geometry is None:
+            raise ValueError("no leg geometry: pass geometry= (params.LEG_GEOMETRY, leg_geometry_from_urdf)")
+        rs, ds = [t if t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+                  else t.to(self.device, torch.float32).contiguous() for t in (root_states, dof_states)]
+        if rs.shape != (self.B, 13) or ds.numel() != self.B * 24:
+            raise ValueError(f"expected root_states [{self.B},13] and dof_states [{self.B},12,2], got "
+                             f"{tuple(rs.shape)} and {tuple(ds.shape)}")
+        self.engine.kinematics(self.geometry, root_states=rs, dof_states=ds, feet=self.feet, thighs=self.thighs,
+                               pos_feet=self.pos_feet, foot_pos_base=self.foot_pos_base,
+                               foot_vel_base=self.foot_vel_base, jac=self.jac)
+        return rs
+
+    def step(self, iter_counter, vel_body_des, yaw_rate_des, root_states, dof_states):
+        """The whole loop body of isaacgym_a1.py:117-162 for every robot, nothing computed by
+        the caller: kinematics, then ``tick``, then ``leg_torques``; returns tau [B,12]
+        (device).  root_states [B,13] and dof_states [B,12,2] are Isaac Gym's actor
+        root-state and dof-state tensors as they lie on the device."""
+        rs = self.kinematics(root_states, dof_states)
+        self.tick(iter_counter, vel_body_des, yaw_rate_des, self.feet, root_states=rs)
+        return self.leg_torques(iter_counter, vel_body_des, yaw_rate_des, self.thighs, self.pos_feet,
+                                self.foot_pos_base, self.foot_vel_base, self.jac, root_states=rs)

@@ -373,3 +373,45 @@ class LinearMpc:
             code = self.lib.mpcqp_leg_torques(self._ctx, B, 0, _ptr(tick), int(iterations_between_mpc), _ptr(quat),
                                               _ptr(pos), _ptr(vel), _ptr(rot), *tail)
         _lib.check(self._ctx, code, "mpcqp_leg_torques")
+
+    def kinematics(self, geom, q=None, qdot=None, quat=None, pos=None, vel=None, omega=None, rot=None,
+                   root_states=None, dof_states=None, feet=None, thighs=None, pos_feet=None, foot_pos_base=None,
+                   foot_vel_base=None, jac=None, stream=None):
+        """Leg kinematics of every robot (include/mpcqp.h mpcqp_kinematics; RobotData.update,
+        robot_data.py:59-108): foot and thigh positions, foot Jacobians and foot velocities
+        in one launch -- the ``feet`` of ``solve`` and the five kinematic inputs of
+        ``leg_torques``.
+
+        Every argument is a preallocated contiguous device tensor: geom [B,KIN_STRIDE]
+        float64 (params.pack_leg_geometry), the rest float32.  Inputs: quat [B,4] (w, x, y,
+        z), pos / vel / omega [B,3], optional rot [B,3,3], q / qdot [B,12]; or ``root_states``
+        [B,13] and ``dof_states`` [B,12,2] (Isaac Gym layout) in their place.  Outputs, each
+        optional: feet, thighs, pos_feet, foot_pos_base, foot_vel_base [B,4,3], jac
+        [B,4,3,3]."""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        B = int(geom.shape[0])
+        tail = (_ptr(geom), _ptr(feet), _ptr(thighs), _ptr(pos_feet), _ptr(foot_pos_base), _ptr(foot_vel_base),
+                _ptr(jac), ctypes.c_void_p(stream.cuda_stream))
+        if (root_states is None) != (dof_states is None):
+            raise ValueError("kinematics: root_states and dof_states go together")
+        if root_states is not None:
+            code = self.lib.mpcqp_kinematics_root_states(self._ctx, B, 0, _ptr(root_states), _ptr(dof_states), *tail)
+        else:
+            code = self.lib.mpcqp_kinematics(self._ctx, B, 0, _ptr(quat), _ptr(pos), _ptr(vel), _ptr(omega),
+                                             _ptr(rot), _ptr(q), _ptr(qdot), *tail)
+        _lib.check(self._ctx, code, "mpcqp_kinematics")
+
+    def bind_kinematics(self, geom, quat, pos, vel, omega, rot, q, qdot, feet=None, thighs=None, pos_feet=None,
+                        foot_pos_base=None, foot_vel_base=None, jac=None):
+        """kinematics() (split state inputs) with its device pointers resolved once: returns
+        ``launch(stream)`` (see bind_solve)."""
+        lib, ctx = self.lib, self._ctx
+        B = int(geom.shape[0])
+        keep = (quat, pos, vel, omega, rot, q, qdot, geom, feet, thighs, pos_feet, foot_pos_base, foot_vel_base, jac)
+        args = (ctx, B, 0) + tuple(_ptr(t) for t in keep)
+
+        def launch(stream):
+            _lib.check(ctx, lib.mpcqp_kinematics(*args, ctypes.c_void_p(stream.cuda_stream)), "mpcqp_kinematics")
+        launch.buffers = keep
+        return launch

@@ -44,6 +44,14 @@ SWING_PRESETS = {"aliengo": dict(swing_height=0.1, kp=200.0, kd=20.0),
 # hip x offset, hip y + thigh y offset (a1.urdf:90,212,254; aliengo.urdf:99,254,297)
 HIP_OFFSETS = {"a1": (0.183, 0.047 + 0.08505), "aliengo": (0.2399, 0.051 + 0.083)}
 
+# leg geometry (hip_x, hip_y, thigh_y, l_thigh, l_calf): the xyz of the FL hip, thigh, calf
+# and foot joints (a1.urdf:212,254,282,310; aliengo.urdf:254,297,326,355); the other legs
+# mirror it (x sign + + - -, y sign + - + - for FL, FR, RL, RR)
+LEG_GEOMETRY = {"a1": (0.183, 0.047, 0.08505, 0.2, 0.2), "aliengo": (0.2399, 0.051, 0.083, 0.25, 0.25)}
+KIN_STRIDE = 8      # MPCQP_KIN_STRIDE: float64 geometry record per robot
+LEG_NAMES = ("FL", "FR", "RL", "RR")
+LEG_SIGNS = ((1.0, 1.0), (1.0, -1.0), (-1.0, 1.0), (-1.0, -1.0))
+
 # name: (period, stance offsets, stance durations)    linear_mpc/gait.py:16-22
 GAITS = {
     "standing": (16, (0, 0, 0, 0), (16, 16, 16, 16)),
@@ -85,6 +93,81 @@ def pack_robot(preset, normal=(0.0, 0.0, 1.0), mu=None, fz_max=None):
     rec[R_FZMAX] = preset["fz_max"] if fz_max is None else fz_max
     rec[R_NX:R_NZ + 1] = normal
     return rec
+
+
+def pack_leg_geometry(geometry, batch=None):
+    """MPCQP_KIN_STRIDE records (float64): [hip_x, hip_y, thigh_y, l_thigh, l_calf, 0, 0, 0].
+
+    ``geometry`` is a LEG_GEOMETRY key, five numbers, or a [B,5] array (a mixed fleet).
+    Returns [KIN_STRIDE] for one robot, [B, KIN_STRIDE] with ``batch`` (one record is
+    repeated) or for a [B,5] array."""
+    if isinstance(geometry, str):
+        geometry = LEG_GEOMETRY[geometry]
+    g = np.asarray(geometry, dtype=np.float64)
+    if g.shape[-1:] != (5,) or g.ndim > 2 or not np.isfinite(g).all():
+        raise ValueError("leg geometry: five finite numbers (hip_x, hip_y, thigh_y, l_thigh, l_calf) per robot")
+    rec = np.zeros(g.shape[:-1] + (KIN_STRIDE,), dtype=np.float64)
+    rec[..., :5] = g
+    if batch is not None:
+        if rec.ndim == 1:
+            rec = np.tile(rec, (int(batch), 1))
+        elif rec.shape[0] != int(batch):
+            raise ValueError(f"leg geometry: expected one record or {batch}, got {rec.shape[0]}")
+    return np.ascontiguousarray(rec)
+
+
+def leg_geometry_from_urdf(path):
+    """(hip_x, hip_y, thigh_y, l_thigh, l_calf) from a URDF file, read from the FL chain
+    ``FL_hip_joint`` -> ``FL_thigh_joint`` -> ``FL_calf_joint`` -> ``FL_foot_fixed``.
+
+    Raises ValueError unless all four legs have the topology the kinematics kernel
+    assumes: hip / thigh / calf revolute about x / y / y, the foot fixed, every joint rpy
+    zero, and the offsets of FR, RL, RR the mirror images of FL's."""
+    import xml.etree.ElementTree as ET
+    joints = {j.get("name"): j for j in ET.parse(path).getroot().iter("joint") if j.get("type") is not None}
+
+    def vec(text, what):
+        v = [float(x) for x in (text or "0 0 0").split()]
+        if len(v) != 3:
+            raise ValueError(f"{what}: expected three numbers, got {text!r}")
+        return v
+
+    def read(leg, part, axis):
+        name = f"{leg}_{part}"
+        j = joints.get(name)
+        if j is None:
+            raise ValueError(f"{path}: no joint {name}")
+        origin = j.find("origin")
+        xyz = vec(origin.get("xyz") if origin is not None else None, name + " xyz")
+        rpy = vec(origin.get("rpy") if origin is not None else None, name + " rpy")
+        if any(r != 0.0 for r in rpy):
+            raise ValueError(f"{name}: joint rpy {rpy} is not zero")
+        if axis is None:
+            if j.get("type") != "fixed":
+                raise ValueError(f"{name}: expected a fixed joint, got {j.get('type')}")
+        else:
+            ax = j.find("axis")
+            got = vec(ax.get("xyz") if ax is not None else "1 0 0", name + " axis")   # URDF's default axis
+            if j.get("type") not in ("revolute", "continuous") or got != axis:
+                raise ValueError(f"{name}: expected a revolute joint about {axis}, got {j.get('type')} about {got}")
+        return xyz
+
+    chains = {}
+    for leg in LEG_NAMES:
+        chains[leg] = (read(leg, "hip_joint", [1.0, 0.0, 0.0]), read(leg, "thigh_joint", [0.0, 1.0, 0.0]),
+                       read(leg, "calf_joint", [0.0, 1.0, 0.0]), read(leg, "foot_fixed", None))
+    hip, thigh, calf, foot = chains["FL"]
+    geom = (hip[0], hip[1], thigh[1], -calf[2], -foot[2])
+    if hip[2] != 0.0 or thigh[0] != 0.0 or thigh[2] != 0.0 or calf[:2] != [0.0, 0.0] or foot[:2] != [0.0, 0.0]:
+        raise ValueError(f"FL: joint offsets {chains['FL']} are not (x, y, 0), (0, y, 0), (0, 0, -l1), (0, 0, -l2)")
+    if min(geom) <= 0.0:
+        raise ValueError(f"FL: expected positive hip_x, hip_y, thigh_y and link lengths, got {geom}")
+    for leg, (sx, sy) in zip(LEG_NAMES, LEG_SIGNS):
+        want = ([sx * geom[0], sy * geom[1], 0.0], [0.0, sy * geom[2], 0.0], [0.0, 0.0, -geom[3]],
+                [0.0, 0.0, -geom[4]])
+        if chains[leg] != want:
+            raise ValueError(f"{leg}: joint offsets {chains[leg]} do not mirror FL's {want}")
+    return geom
 
 
 def robot_from_config(robot_config, mu=MU, normal=(0.0, 0.0, 1.0)):
