@@ -344,6 +344,75 @@ int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, c
                                  float* pos_feet, float* foot_pos_base, float* foot_vel_base, float* jac,
                                  void* stream);
 
+/* ---- the base-state estimator on the device: IMU + leg-kinematics Kalman filter ----
+ *
+ * mpcqp_estimate is one tick, for B robots in one launch, of the linear Kalman filter the
+ * reference derives in doc/state_estimation_kf.md (its second stage, after MIT Cheetah 3)
+ * and never builds: RobotData.update raises NotImplementedError for state_estimation=True.
+ * It fuses the accelerometer with the leg kinematics of the feet in contact, from the
+ * sensor set scripts/mujoco_aliengo.py:101-118 collects (IMU quaternion, gyro,
+ * accelerometer, joint positions and rates, touch state), and writes a root-state tensor in
+ * the layout the *_root_states entry points read, so the estimate feeds them in place.  One
+ * launch, no allocation, synchronisation or host read: it can be captured into a HIP graph
+ * (the filter's state lives in caller memory, so a replay advances it).  One filter per
+ * robot, nothing shared between robots.  Float64 arithmetic on the float32 inputs, each
+ * float32 output rounded once.  The orientation (the doc's first stage) is an input.
+ *
+ *   state x = [p_b, v_b, p_1, p_2, p_3, p_4] in R^18: base position and velocity and the
+ *   four feet (FL, FR, RL, RR), world frame; covariance P 18 x 18.
+ *
+ *   flags        0 or MPCQP_EST_DOF_STATES
+ *   quat         [B][4]  (w, x, y, z), used as given (not normalised); R_q as in mpcqp_kinematics
+ *   gyro, accel  [B][3]  angular rate w_b and the accelerometer's specific force a_b, body frame
+ *   q, qdot      [B][12] joint angles / rates; with MPCQP_EST_DOF_STATES q is a dof-state
+ *                        tensor [B][12][2] and qdot is ignored (may be NULL)
+ *   trust        [B][4]  clipped to [0, 1]: 1 = the foot is in contact, 0 = it swings; a
+ *                        ramp is allowed (the touch sensor, or swing_state == 0)
+ *   geom         [B][MPCQP_KIN_STRIDE]  as for mpcqp_kinematics
+ *   est_state    [B][MPCQP_EST_STRIDE] float64 in/out, 16-byte aligned: x[18], initialised
+ *                        (0 / 1), 5 x 0, P[18][18] row-major (symmetric) at 24, 4 x 0.  An
+ *                        all-zero record is "not initialised": x = 0, P = p0 I.  A caller may
+ *                        seed x, P and initialised = 1 itself.
+ * Outputs, each nullable:
+ *   root_states  [B][13]  pos = p_b, quat (x, y, z, w) copied from the input, lin_vel = v_b,
+ *                        ang_vel = R_q w_b (world frame)
+ *   feet_world   [B][4][3]  p_1 .. p_4
+ *   status       [B]     MPCQP_STATUS_OK, or MPCQP_STATUS_NONFINITE for a robot with a
+ *                        non-finite input: its record is not written and its outputs are
+ *                        formed from the record as it was; no other robot is affected
+ * The tick, with (p_i, J_i) the foot and its Jacobian in the base frame, t_i the clipped
+ * trust, k_i = 1 + (1 - t_i) suspicion and x^-, P^- the record:
+ *   r_i = R_q p_i,  rd_i = R_q (w_b x p_i + J_i qdot_i),  a = R_q a_b - (0, 0, g)
+ *   y = [-r_i (4 x 3);  (1 - t_i) v_b^- - t_i rd_i (4 x 3);  t_i h + (1 - t_i)(p_b,z^- + r_i,z) (4)]
+ *   predict  x = A x^- + B a, P = A P^- A^T + Q;  A = I + dt [p <- v], B = [dt^2/2 I; dt I; 0],
+ *            Q = dt diag(sigma_p 1_3, sigma_v 1_3, sigma_f k_i 1_3 ...)
+ *   C        rows [I, 0, -I at foot i], [0, I, 0], z of foot i;
+ *            R = diag(r_p 1_12, r_v k_i 1_3 ..., r_z k_i ...)
+ *   update   K = P C^T (C P C^T + R)^-1, x += K (y - C x), P -= K C P, P <- (P + P^T) / 2
+ * carried out as 28 scalar updates (R is diagonal).  The Cheetah software's shrinking of
+ * P's xy block is not part of it (deviations).
+ *
+ * An unknown flag bit, batch <= 0, a NULL required pointer or a misaligned est_state
+ * return MPCQP_ERR_ARG. */
+#define MPCQP_EST_STRIDE 352      /* doubles per robot: x[18], initialised, 5 x 0, P[18][18] row-major at 24, 4 x 0 */
+#define MPCQP_EST_DOF_STATES 1    /* flags: q points at a dof-state tensor [B][12][2] (pos, vel); qdot is ignored */
+int mpcqp_estimate(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* quat, const float* gyro,
+                   const float* accel, const float* q, const float* qdot, const float* trust,
+                   const double* geom, double* est_state, float* root_states, float* feet_world,
+                   int32_t* status, void* stream);
+
+/* Estimator constants (doc/state_estimation_kf.md; the noise defaults are the Cheetah 3
+ * software's published values folded into rates): the time step dt (0.001) and gravity
+ * (9.81), the process rates sigma_p (0.001), sigma_v (0.0098), sigma_f (0.002), the
+ * measurement variances r_p (0.001), r_v (0.1), r_z (0.001), the suspicion factor (100)
+ * that inflates the noise of a foot that is not trusted, the initial variance p0 (100) and
+ * the contact height (0), the world z of a foot in contact.  A non-finite value, dt <= 0,
+ * any of r_p, r_v, r_z, p0 <= 0, a sigma < 0 or suspicion < 0 returns MPCQP_ERR_ARG and
+ * leaves the previous constants in force. */
+int mpcqp_set_estimator(mpcqp_ctx* ctx, double dt, double gravity, double sigma_p, double sigma_v,
+                        double sigma_f, double r_p, double r_v, double r_z, double suspicion,
+                        double p0, double contact_height);
+
 int mpcqp_destroy(mpcqp_ctx* ctx);
 
 const char* mpcqp_last_error(const mpcqp_ctx* ctx);

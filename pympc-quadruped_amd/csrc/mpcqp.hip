@@ -348,6 +348,7 @@ __device__ __forceinline__ int wave_argmin_f32(double v, double& vmin_out) {
 #include "mpcqp_plan.h"
 #include "mpcqp_swing.h"
 #include "mpcqp_kinematics.h"
+#include "mpcqp_estimator.h"
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 
 // Workgroups are dealt round-robin over the 8 XCDs (block bid runs on XCD bid % 8,
@@ -682,6 +683,7 @@ struct mpcqp_ctx {
   double vel_gain;
   double kp_swing[9];
   double kd_swing[9];
+  EstParams est;      // estimator constants (mpcqp_set_estimator)
   std::string err;
 };
 
@@ -840,6 +842,8 @@ int mpcqp_create(const mpcqp_params* p, int32_t device, mpcqp_ctx** out) {
     ctx->kd_swing[i] = i % 4 == 0 ? 20.0 : 0.0;
   }
   ctx->max_pos_error = 0.1;   // mpc.py:121
+  // the estimator: the Cheetah 3 software's noise values folded into rates (include/mpcqp.h)
+  ctx->est = EstParams{0, 0.001, 9.81, 0.001, 0.0098, 0.002, 0.001, 0.1, 0.001, 100.0, 100.0, 0.0};
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->ncu = prop.multiProcessorCount;
   if (ctx->ncu <= 0) ctx->ncu = 256;
@@ -1309,6 +1313,48 @@ int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, c
                                  void* stream) {
   return launch_kinematics(ctx, batch, flags, 1, root_states, nullptr, nullptr, nullptr, nullptr, dof_states,
                            nullptr, geom, feet, thighs, pos_feet, foot_pos_base, foot_vel_base, jac, stream);
+}
+
+// ---- the base-state estimator (mpcqp_estimator.h): the Kalman filter doc/state_estimation_kf.md
+// derives (second stage) on the sensors scripts/mujoco_aliengo.py:101-118 collects; the reference
+// raises NotImplementedError in its place (RobotData.update, state_estimation=True).  An invalid
+// constant leaves the previous set in force.
+int mpcqp_set_estimator(mpcqp_ctx* ctx, double dt, double gravity, double sigma_p, double sigma_v, double sigma_f,
+                        double r_p, double r_v, double r_z, double suspicion, double p0, double contact_height) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  const double all[11] = {dt, gravity, sigma_p, sigma_v, sigma_f, r_p, r_v, r_z, suspicion, p0, contact_height};
+  for (double v : all)
+    if (!std::isfinite(v)) return set_err(ctx, MPCQP_ERR_ARG, "non-finite estimator constant");
+  if (!(dt > 0.0)) return set_err(ctx, MPCQP_ERR_ARG, "estimator: dt <= 0");
+  if (!(r_p > 0.0) || !(r_v > 0.0) || !(r_z > 0.0) || !(p0 > 0.0))
+    return set_err(ctx, MPCQP_ERR_ARG, "estimator: r_p, r_v, r_z and p0 must be > 0");
+  if (sigma_p < 0.0 || sigma_v < 0.0 || sigma_f < 0.0 || suspicion < 0.0)
+    return set_err(ctx, MPCQP_ERR_ARG, "estimator: a process rate or the suspicion factor is < 0");
+  ctx->est = EstParams{0, dt, gravity, sigma_p, sigma_v, sigma_f, r_p, r_v, r_z, suspicion, p0, contact_height};
+  return MPCQP_OK;
+}
+
+int mpcqp_estimate(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* quat, const float* gyro,
+                   const float* accel, const float* q, const float* qdot, const float* trust, const double* geom,
+                   double* est_state, float* root_states, float* feet_world, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (batch <= 0) return set_err(ctx, MPCQP_ERR_ARG, "estimate: batch <= 0");
+  if (flags & ~MPCQP_EST_DOF_STATES) return set_err(ctx, MPCQP_ERR_ARG, "unknown estimator flags");
+  const int dof_layout = (flags & MPCQP_EST_DOF_STATES) ? 1 : 0;
+  if (!quat || !gyro || !accel || !q || (!dof_layout && !qdot) || !trust || !geom || !est_state)
+    return set_err(ctx, MPCQP_ERR_ARG, "null estimator input/state pointer");
+  if ((uintptr_t)est_state & 15) return set_err(ctx, MPCQP_ERR_ARG, "est_state is not 16-byte aligned");
+  static_assert(EST_STRIDE == MPCQP_EST_STRIDE, "record stride");
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  EstParams ep = ctx->est;
+  ep.dof_layout = dof_layout;
+  hipLaunchKernelGGL(mpcqp_estimate_kernel, dim3((batch + kEstRobots - 1) / kEstRobots), dim3(kEstThreads), 0,
+                     (hipStream_t)stream, ep, (int)batch, quat, gyro, accel, q, qdot, trust, geom, est_state,
+                     root_states, feet_world, status);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("estimator launch: ") + hipGetErrorString(e));
+  return MPCQP_OK;
 }
 
 int mpcqp_destroy(mpcqp_ctx* ctx) {

@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = (
     "mpcqp_set_swing",
     "mpcqp_kinematics",
     "mpcqp_kinematics_root_states",
+    "mpcqp_estimate",
+    "mpcqp_set_estimator",
 )
 ABI_VERSION = 6
 WARM_BYTES = 128     # MPCQP_WARM_BYTES: warm-start memory per robot
@@ -55,6 +57,8 @@ PLAN_REFERENCE = 1      # MPCQP_PLAN_REFERENCE: build X_ref (+ gait table) this 
 PLAN_NO_INTEGRATE = 2   # MPCQP_PLAN_NO_INTEGRATE: skip the desired-pose integrators
 SWING_STRIDE = 32   # MPCQP_SWING_STRIDE: float64 swing-generator state per robot (8 per leg)
 KIN_STRIDE = 8      # MPCQP_KIN_STRIDE: float64 leg geometry per robot (5 used)
+EST_STRIDE = 352    # MPCQP_EST_STRIDE: float64 estimator record per robot (x[18], initialised, P at 24)
+EST_DOF_STATES = 1  # MPCQP_EST_DOF_STATES: q is a dof-state tensor [B,12,2], qdot ignored
 
 
 class MpcqpParams(ctypes.Structure):
@@ -125,6 +129,10 @@ def load():
     lib.mpcqp_kinematics.argtypes = [vp, i32, i32] + [vp] * 14 + [vp]
     lib.mpcqp_kinematics_root_states.restype = ctypes.c_int
     lib.mpcqp_kinematics_root_states.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
+    lib.mpcqp_estimate.restype = ctypes.c_int
+    lib.mpcqp_estimate.argtypes = [vp, i32, i32] + [vp] * 11 + [vp]
+    lib.mpcqp_set_estimator.restype = ctypes.c_int
+    lib.mpcqp_set_estimator.argtypes = [vp] + [ctypes.c_double] * 11
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise MpcqpError("libmpcqp ABI version mismatch")
     _lib = lib

@@ -415,3 +415,42 @@ class LinearMpc:
             _lib.check(ctx, lib.mpcqp_kinematics(*args, ctypes.c_void_p(stream.cuda_stream)), "mpcqp_kinematics")
         launch.buffers = keep
         return launch
+
+    def set_estimator(self, dt=0.001, gravity=9.81, sigma_p=0.001, sigma_v=0.0098, sigma_f=0.002, r_p=0.001,
+                      r_v=0.1, r_z=0.001, suspicion=100.0, p0=100.0, contact_height=0.0):
+        """Estimator constants (include/mpcqp.h mpcqp_set_estimator; doc/state_estimation_kf.md):
+        time step and gravity, the process rates of base position, base velocity and feet, the
+        measurement variances of the leg position, leg velocity and contact-height rows, the
+        suspicion factor of an untrusted foot, the initial variance and the contact height.
+        Like set_swing, every call sets all of them (an omitted one returns to its default);
+        an invalid value raises and keeps the previous constants."""
+        code = self.lib.mpcqp_set_estimator(self._ctx, float(dt), float(gravity), float(sigma_p), float(sigma_v),
+                                            float(sigma_f), float(r_p), float(r_v), float(r_z), float(suspicion),
+                                            float(p0), float(contact_height))
+        _lib.check(self._ctx, code, "mpcqp_set_estimator")
+        self.estimator_constants = dict(dt=dt, gravity=gravity, sigma_p=sigma_p, sigma_v=sigma_v, sigma_f=sigma_f,
+                                        r_p=r_p, r_v=r_v, r_z=r_z, suspicion=suspicion, p0=p0,
+                                        contact_height=contact_height)
+
+    def estimate(self, est_state, quat, gyro, accel, trust, geom, q=None, qdot=None, dof_states=None,
+                 root_states=None, feet_world=None, status=None, stream=None):
+        """One tick of every robot's base-state Kalman filter (include/mpcqp.h mpcqp_estimate):
+        IMU and leg kinematics in, base position / velocity and the feet in the world frame
+        out, in one launch on the current stream.
+
+        Every argument is a preallocated contiguous device tensor: est_state [B,EST_STRIDE]
+        and geom [B,KIN_STRIDE] float64, status [B] int32, the rest float32.  Inputs: quat
+        [B,4] (w, x, y, z), gyro / accel [B,3] (body frame), trust [B,4], q / qdot [B,12] or
+        ``dof_states`` [B,12,2] in their place.  Outputs, each optional: root_states [B,13]
+        (Isaac Gym layout, what the ``*_root_states`` calls read), feet_world [B,4,3],
+        status [B]."""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        if (dof_states is None) == (q is None):
+            raise ValueError("estimate: give q and qdot, or dof_states")
+        B = int(est_state.shape[0])
+        flags, jq, jqd = (_lib.EST_DOF_STATES, dof_states, None) if dof_states is not None else (0, q, qdot)
+        code = self.lib.mpcqp_estimate(self._ctx, B, flags, _ptr(quat), _ptr(gyro), _ptr(accel), _ptr(jq), _ptr(jqd),
+                                       _ptr(trust), _ptr(geom), _ptr(est_state), _ptr(root_states),
+                                       _ptr(feet_world), _ptr(status), ctypes.c_void_p(stream.cuda_stream))
+        _lib.check(self._ctx, code, "mpcqp_estimate")
