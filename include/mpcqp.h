@@ -356,7 +356,8 @@ int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, c
  * launch, no allocation, synchronisation or host read: it can be captured into a HIP graph
  * (the filter's state lives in caller memory, so a replay advances it).  One filter per
  * robot, nothing shared between robots.  Float64 arithmetic on the float32 inputs, each
- * float32 output rounded once.  The orientation (the doc's first stage) is an input.
+ * float32 output rounded once.  The orientation (the doc's first stage) and the trust are
+ * inputs: mpcqp_attitude computes both from the raw sensors.
  *
  *   state x = [p_b, v_b, p_1, p_2, p_3, p_4] in R^18: base position and velocity and the
  *   four feet (FL, FR, RL, RR), world frame; covariance P 18 x 18.
@@ -412,6 +413,73 @@ int mpcqp_estimate(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* qu
 int mpcqp_set_estimator(mpcqp_ctx* ctx, double dt, double gravity, double sigma_p, double sigma_v,
                         double sigma_f, double r_p, double r_v, double r_z, double suspicion,
                         double p0, double contact_height);
+
+/* ---- the orientation filter and the contact trust on the device, ahead of the estimator ----
+ *
+ * mpcqp_attitude produces, for B robots in one launch, the two inputs of mpcqp_estimate a
+ * robot's sensors do not deliver: the orientation `quat`, by the gyro / accelerometer filter
+ * of doc/state_estimation_kf.md section 2 (the document's first stage), and the contact
+ * `trust`, ramped in and out over the stance phase as in the Cheetah 3 filter the document
+ * follows and gated by the touch sensor (scripts/mujoco_aliengo.py:101-118, touch_state).  The
+ * stance phase is decided on the integers mpcqp_leg_torques decides it on, so trust is 0
+ * exactly where that call reports swing_state > 0.  One thread per robot, one launch, no
+ * atomics, allocation, synchronisation or host read: it can be captured into a HIP graph (the
+ * filter's record lives in caller memory, so a replay advances it).  Float64 arithmetic on the
+ * float32 inputs, each float32 output rounded once.
+ *
+ *   flags        0 (reserved)
+ *   gyro, accel  [B][3]  angular rate w_b and the accelerometer's specific force a_b, body
+ *                        frame (at rest a_b = R^T (0, 0, g)), as for mpcqp_estimate
+ *   tick         [B]     control-iteration counters, as for mpcqp_leg_torques; nullable
+ *                        without gait
+ *   iterations_between_mpc, gait [B][MPCQP_GAIT_STRIDE]   as for mpcqp_leg_torques; gait nullable
+ *   touch        [B][4]  the touch sensor per foot (FL, FR, RL, RR); nullable
+ *   att_state    [B][MPCQP_ATT_STRIDE] float64 in/out, 16-byte aligned: q (w, x, y, z),
+ *                        initialised (0 / 1), gyro bias b[3].  An all-zero record is "not
+ *                        initialised".  A caller may seed q, b and initialised = 1 itself.
+ * Outputs, each nullable (a NULL output is not written):
+ *   quat         [B][4]  (w, x, y, z), unit length; its sign is not canonicalised
+ *   gyro_out     [B][3]  w_b - b, the input bitwise while b = 0
+ *   trust        [B][4]  in [0, 1]; needs gait and tick, or touch
+ *   status       [B]     MPCQP_STATUS_OK, or MPCQP_STATUS_NONFINITE for a robot with a
+ *                        non-finite gyro, accel, touch or record value: its record is not
+ *                        written, quat / gyro_out are formed from the record as it was
+ *                        (identity, b = 0 if not initialised), a non-finite touch makes its
+ *                        four trusts 0; no other robot is affected
+ * The orientation tick, with n = |a_b| and m = a_b / n (n > 0):
+ *   record not initialised: q = normalise(1 + m_z, m_y, -m_x, 0), the shortest arc with
+ *     R(q)^T e_z = m and zero yaw ((0, 1, 0, 0) for m_z < -1 + 1e-12, identity for n = 0),
+ *     b = 0, initialised = 1; no integration on this tick
+ *   else  u = R(q)^T e_z (the third row of mpcqp_kinematics' R_q),  e = m x u (0 for n = 0),
+ *         gamma = clamp(1 - |n - g| / g, 0, 1) (0 for n = 0): the document's kappa heuristic,
+ *         omega = w_b - b + kappa_ref gamma e,   b <- b - bias_gain gamma e dt,
+ *         theta = omega dt,  dq = (cos(|theta| / 2), sin(|theta| / 2) theta / |theta|)
+ *         ((1, theta / 2) for |theta| < 1e-8),  q <- normalise(q (x) dq)
+ * which is the document's R_{k+1} = R_k exp([w_b + kappa w_corr]x dt); the bias term is the
+ * integral term of Mahony's filter (the document's ref. [3]) and is off by default.  Yaw is
+ * not corrected: it is unobservable without exteroception, as the document says.
+ * The trust of a leg, with swing_decide's cs and nsw = (period - dur) ibm (mpcqp_leg_torques):
+ *   0 in swing (1 <= cs <= nsw); 1 for a leg that never swings (nsw <= 0) or a malformed record;
+ *   in stance nst = dur ibm, k = (cs == 0 ? nst : cs - nsw) in 1 .. nst, phi = (k - 1/2) / nst,
+ *   trust = min(1, phi / w, (1 - phi) / w) with w = trust_window (w = 0: 1)
+ *   with touch: touch <= touch_threshold forces 0; without gait: trust = (touch > threshold)
+ *
+ * A non-zero flag, batch <= 0, a NULL gyro, accel or att_state, a misaligned att_state, trust
+ * wanted with neither gait and tick nor touch, gait without tick, or iterations_between_mpc
+ * < 1 with a gait return MPCQP_ERR_ARG. */
+#define MPCQP_ATT_STRIDE 8        /* doubles per robot: q (w, x, y, z), initialised, gyro bias b[3] */
+int mpcqp_attitude(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* gyro, const float* accel,
+                   const int32_t* tick, int32_t iterations_between_mpc, const int32_t* gait,
+                   const float* touch, double* att_state, float* quat, float* gyro_out, float* trust,
+                   int32_t* status, void* stream);
+
+/* Constants of mpcqp_attitude: the time step dt (0.001) and gravity (9.81), the correction
+ * gain kappa_ref in 1/s (0.1, the document's value), the bias gain (0: no bias estimate), the
+ * trust window as a fraction of the stance (0.2) and the touch threshold (0).  A non-finite
+ * value, dt <= 0, gravity <= 0, kappa_ref < 0, bias_gain < 0 or a trust_window outside
+ * [0, 0.5] returns MPCQP_ERR_ARG and leaves the previous constants in force. */
+int mpcqp_set_attitude(mpcqp_ctx* ctx, double dt, double gravity, double kappa_ref, double bias_gain,
+                       double trust_window, double touch_threshold);
 
 int mpcqp_destroy(mpcqp_ctx* ctx);
 

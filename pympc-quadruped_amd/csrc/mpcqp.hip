@@ -349,6 +349,7 @@ __device__ __forceinline__ int wave_argmin_f32(double v, double& vmin_out) {
 #include "mpcqp_swing.h"
 #include "mpcqp_kinematics.h"
 #include "mpcqp_estimator.h"
+#include "mpcqp_attitude.h"
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 
 // Workgroups are dealt round-robin over the 8 XCDs (block bid runs on XCD bid % 8,
@@ -684,6 +685,7 @@ struct mpcqp_ctx {
   double kp_swing[9];
   double kd_swing[9];
   EstParams est;      // estimator constants (mpcqp_set_estimator)
+  AttParams att;      // orientation-filter and contact-trust constants (mpcqp_set_attitude)
   std::string err;
 };
 
@@ -844,6 +846,9 @@ int mpcqp_create(const mpcqp_params* p, int32_t device, mpcqp_ctx** out) {
   ctx->max_pos_error = 0.1;   // mpc.py:121
   // the estimator: the Cheetah 3 software's noise values folded into rates (include/mpcqp.h)
   ctx->est = EstParams{0, 0.001, 9.81, 0.001, 0.0098, 0.002, 0.001, 0.1, 0.001, 100.0, 100.0, 0.0};
+  // the orientation filter: the document's kappa_ref, no bias estimate; the trust ramps over
+  // the first and last fifth of the stance
+  ctx->att = AttParams{0.001, 9.81, 0.1, 0.0, 0.2, 0.0};
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->ncu = prop.multiProcessorCount;
   if (ctx->ncu <= 0) ctx->ncu = 256;
@@ -1354,6 +1359,48 @@ int mpcqp_estimate(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* qu
                      root_states, feet_world, status);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("estimator launch: ") + hipGetErrorString(e));
+  return MPCQP_OK;
+}
+
+// ---- the orientation filter and the contact trust (mpcqp_attitude.h): the first stage of
+// doc/state_estimation_kf.md (section 2) and the stance-phase trust ramp, producing the `quat`
+// and `trust` of mpcqp_estimate from the raw sensors scripts/mujoco_aliengo.py:101-118 collects.
+// An invalid constant leaves the previous set in force.
+int mpcqp_set_attitude(mpcqp_ctx* ctx, double dt, double gravity, double kappa_ref, double bias_gain,
+                       double trust_window, double touch_threshold) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  const double all[6] = {dt, gravity, kappa_ref, bias_gain, trust_window, touch_threshold};
+  for (double v : all)
+    if (!std::isfinite(v)) return set_err(ctx, MPCQP_ERR_ARG, "non-finite attitude constant");
+  if (!(dt > 0.0) || !(gravity > 0.0)) return set_err(ctx, MPCQP_ERR_ARG, "attitude: dt and gravity must be > 0");
+  if (kappa_ref < 0.0 || bias_gain < 0.0) return set_err(ctx, MPCQP_ERR_ARG, "attitude: kappa_ref or bias_gain is < 0");
+  if (trust_window < 0.0 || trust_window > 0.5)
+    return set_err(ctx, MPCQP_ERR_ARG, "attitude: trust_window outside [0, 0.5]");
+  ctx->att = AttParams{dt, gravity, kappa_ref, bias_gain, trust_window, touch_threshold};
+  return MPCQP_OK;
+}
+
+int mpcqp_attitude(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* gyro, const float* accel,
+                   const int32_t* tick, int32_t iterations_between_mpc, const int32_t* gait, const float* touch,
+                   double* att_state, float* quat, float* gyro_out, float* trust, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown attitude flags");
+  if (batch <= 0) return set_err(ctx, MPCQP_ERR_ARG, "attitude: batch <= 0");
+  if (!gyro || !accel || !att_state) return set_err(ctx, MPCQP_ERR_ARG, "null attitude input/state pointer");
+  if ((uintptr_t)att_state & 15) return set_err(ctx, MPCQP_ERR_ARG, "att_state is not 16-byte aligned");
+  if (gait && !tick) return set_err(ctx, MPCQP_ERR_ARG, "attitude: gait given without tick");
+  if (trust && !gait && !touch)
+    return set_err(ctx, MPCQP_ERR_ARG, "attitude: trust wanted with neither gait and tick nor touch");
+  if (gait && iterations_between_mpc < 1) return set_err(ctx, MPCQP_ERR_ARG, "attitude: iterations_between_mpc < 1");
+  static_assert(ATT_STRIDE == MPCQP_ATT_STRIDE, "record stride");
+  static_assert(ATT_STATUS_OK == MPCQP_STATUS_OK && ATT_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  hipLaunchKernelGGL(mpcqp_attitude_kernel, dim3((batch + kAttThreads - 1) / kAttThreads), dim3(kAttThreads), 0,
+                     (hipStream_t)stream, ctx->att, (int)batch, (int)iterations_between_mpc, gyro, accel, tick, gait,
+                     touch, att_state, quat, gyro_out, trust, status);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("attitude launch: ") + hipGetErrorString(e));
   return MPCQP_OK;
 }
 

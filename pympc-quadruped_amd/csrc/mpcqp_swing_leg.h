@@ -25,6 +25,25 @@ constexpr int SW_ARMED = 0, SW_REMAIN = 1, SW_INIT = 2, SW_FINAL = 5, SW_LEG_STR
 
 constexpr int SWING_STANCE = 0, SWING_ACTIVE = 1, SWING_FINISHED = 2;
 
+// The integers swing_decide decides on: *nsw control iterations per swing, *c = tick mod the
+// gait's span and *cs = c shifted by the leg's swing offset; the leg swings for
+// 1 <= cs <= nsw.  False for a leg that never swings (nsw <= 0) or a malformed record.
+// Shared with the contact trust of mpcqp_attitude_robot.h, so the two cannot disagree.
+__host__ __device__ inline bool swing_counts(int tick, int ibm, int period, int off, int dur, long long* cs,
+                                             long long* nsw, long long* c = nullptr) {
+  if (period <= 0 || ibm <= 0) return false;
+  const long long span = (long long)ibm * period;
+  *nsw = (long long)(period - dur) * ibm;
+  if (*nsw <= 0) return false;
+  long long cc = (long long)tick % span;
+  if (cc < 0) cc += span;
+  long long s = (cc - (long long)(off + dur) * ibm) % span;
+  if (s < 0) s += span;
+  *cs = s;
+  if (c != nullptr) *c = cc;
+  return true;
+}
+
 // The leg's swing state at control iteration `tick` (gait.py:76-79,102-121).  The
 // decisions -- stance / swing (swing_state > 0) and swing finished (swing_state >= 1) --
 // are taken on integers: with c = tick mod (ibm * period) and cs = c shifted by the leg's
@@ -38,15 +57,10 @@ constexpr int SWING_STANCE = 0, SWING_ACTIVE = 1, SWING_FINISHED = 2;
 __host__ __device__ inline int swing_decide(int tick, int ibm, int period, int off, int dur, double* value) {
 #pragma clang fp contract(off)
   *value = 0.0;
-  if (period <= 0 || ibm <= 0) return SWING_STANCE;
-  const long long span = (long long)ibm * period;
-  const long long nsw = (long long)(period - dur) * ibm;   // control iterations per swing
-  if (nsw <= 0) return SWING_STANCE;
-  long long c = (long long)tick % span;
-  if (c < 0) c += span;
-  long long cs = (c - (long long)(off + dur) * ibm) % span;
-  if (cs < 0) cs += span;
+  long long c, cs, nsw;   // nsw: control iterations per swing
+  if (!swing_counts(tick, ibm, period, off, dur, &cs, &nsw, &c)) return SWING_STANCE;
   if (cs == 0 || cs > nsw) return SWING_STANCE;
+  const long long span = (long long)ibm * period;
   const float phase = (float)((double)c / (double)span);   // phase_state is a float32 array
   double so = (double)off / (double)period + (double)dur / (double)period;
   if (so > 1.0) so -= 1.0;

@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = (
     "mpcqp_kinematics_root_states",
     "mpcqp_estimate",
     "mpcqp_set_estimator",
+    "mpcqp_attitude",
+    "mpcqp_set_attitude",
 )
 ABI_VERSION = 6
 WARM_BYTES = 128     # MPCQP_WARM_BYTES: warm-start memory per robot
@@ -59,6 +61,7 @@ SWING_STRIDE = 32   # MPCQP_SWING_STRIDE: float64 swing-generator state per robo
 KIN_STRIDE = 8      # MPCQP_KIN_STRIDE: float64 leg geometry per robot (5 used)
 EST_STRIDE = 352    # MPCQP_EST_STRIDE: float64 estimator record per robot (x[18], initialised, P at 24)
 EST_DOF_STATES = 1  # MPCQP_EST_DOF_STATES: q is a dof-state tensor [B,12,2], qdot ignored
+ATT_STRIDE = 8      # MPCQP_ATT_STRIDE: float64 orientation record per robot (q[4], initialised, gyro bias[3])
 
 
 class MpcqpParams(ctypes.Structure):
@@ -133,6 +136,10 @@ def load():
     lib.mpcqp_estimate.argtypes = [vp, i32, i32] + [vp] * 11 + [vp]
     lib.mpcqp_set_estimator.restype = ctypes.c_int
     lib.mpcqp_set_estimator.argtypes = [vp] + [ctypes.c_double] * 11
+    lib.mpcqp_attitude.restype = ctypes.c_int
+    lib.mpcqp_attitude.argtypes = [vp, i32, i32, vp, vp, vp, i32] + [vp] * 7 + [vp]
+    lib.mpcqp_set_attitude.restype = ctypes.c_int
+    lib.mpcqp_set_attitude.argtypes = [vp] + [ctypes.c_double] * 6
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise MpcqpError("libmpcqp ABI version mismatch")
     _lib = lib

@@ -454,3 +454,36 @@ class LinearMpc:
                                        _ptr(trust), _ptr(geom), _ptr(est_state), _ptr(root_states),
                                        _ptr(feet_world), _ptr(status), ctypes.c_void_p(stream.cuda_stream))
         _lib.check(self._ctx, code, "mpcqp_estimate")
+
+    def set_attitude(self, dt=0.001, gravity=9.81, kappa_ref=0.1, bias_gain=0.0, trust_window=0.2,
+                     touch_threshold=0.0):
+        """Constants of ``attitude`` (include/mpcqp.h mpcqp_set_attitude; doc/state_estimation_kf.md
+        section 2): time step and gravity, the correction gain kappa_ref (1/s) that pulls pitch
+        and roll towards the accelerometer, the gain of the gyro-bias estimate (0: none), the
+        trust window as a fraction of the stance and the touch threshold.  Like set_estimator,
+        every call sets all of them; an invalid value raises and keeps the previous constants."""
+        code = self.lib.mpcqp_set_attitude(self._ctx, float(dt), float(gravity), float(kappa_ref), float(bias_gain),
+                                           float(trust_window), float(touch_threshold))
+        _lib.check(self._ctx, code, "mpcqp_set_attitude")
+        self.attitude_constants = dict(dt=dt, gravity=gravity, kappa_ref=kappa_ref, bias_gain=bias_gain,
+                                       trust_window=trust_window, touch_threshold=touch_threshold)
+
+    def attitude(self, att_state, gyro, accel, tick=None, iterations_between_mpc=0, gait=None, touch=None,
+                 quat=None, gyro_out=None, trust=None, status=None, stream=None):
+        """One tick of every robot's orientation filter, and the contact trust of its feet
+        (include/mpcqp.h mpcqp_attitude): gyro and accelerometer in, the ``quat`` and ``trust``
+        of ``estimate`` out, in one launch on the current stream.
+
+        Every argument is a preallocated contiguous device tensor: att_state [B,ATT_STRIDE]
+        float64, tick [B] / gait [B,9] / status [B] int32, the rest float32.  Inputs: gyro /
+        accel [B,3] (body frame); for the trust, tick and gait with ``iterations_between_mpc``
+        (as for ``leg_torques``) and / or touch [B,4].  Outputs, each optional: quat [B,4]
+        (w, x, y, z), gyro_out [B,3] (gyro less the estimated bias), trust [B,4], status [B]."""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        B = int(att_state.shape[0])
+        code = self.lib.mpcqp_attitude(self._ctx, B, 0, _ptr(gyro), _ptr(accel), _ptr(tick),
+                                       int(iterations_between_mpc), _ptr(gait), _ptr(touch), _ptr(att_state),
+                                       _ptr(quat), _ptr(gyro_out), _ptr(trust), _ptr(status),
+                                       ctypes.c_void_p(stream.cuda_stream))
+        _lib.check(self._ctx, code, "mpcqp_attitude")
