@@ -222,7 +222,9 @@ int mpcqp_plan_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const f
                            float* xref, float* contact, void* stream);
 
 /* Planner constants: dt_control (linear_mpc_configs.py:6, default 0.001), gravity
- * (:13, 9.81) and the reference-position clamp (mpc.py:121, 0.1). */
+ * (:13, 9.81) and the reference-position clamp (mpc.py:121, 0.1).  MPCQP_ERR_ARG for a
+ * non-finite constant or a negative dt_control / max_pos_error; the constants then stay
+ * as they were. */
 int mpcqp_set_planner(mpcqp_ctx* ctx, double dt_control, double gravity, double max_pos_error);
 
 /* Stance-leg joint torques tau = Jv_leg^T (-f_leg) (leg_controller.py:86-89,

@@ -1127,7 +1127,11 @@ int mpcqp_set_weights(mpcqp_ctx* ctx, const double* Q, const double* R) {
 }
 
 int mpcqp_set_planner(mpcqp_ctx* ctx, double dt_control, double gravity, double max_pos_error) {
-  if (!ctx || !(dt_control >= 0.0) || !(max_pos_error >= 0.0)) return MPCQP_ERR_ARG;
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (!std::isfinite(dt_control) || !std::isfinite(gravity) || !std::isfinite(max_pos_error))
+    return set_err(ctx, MPCQP_ERR_ARG, "non-finite planner constant");
+  if (dt_control < 0.0 || max_pos_error < 0.0)
+    return set_err(ctx, MPCQP_ERR_ARG, "negative planner constant (dt_control, max_pos_error)");
   ctx->dt_control = dt_control;
   ctx->gravity = gravity;
   ctx->max_pos_error = max_pos_error;

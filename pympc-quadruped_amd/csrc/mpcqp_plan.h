@@ -106,7 +106,10 @@ __global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
     const float a_y = 2.f * ((qw * qz) + (qx * qy));
     const float b_y = (1.f - 2.f * ((qy * qy) + (qz * qz)));
     const double roll = atan2((double)a_r, (double)b_r);
-    const double pitch = asin(fmin(fmax((double)a_p, -1.0), 1.0));   // math.asin raises instead
+    // math.asin raises past +-1 instead; the comparisons (not fmin / fmax, which drop a
+    // NaN for the bound) let a NaN quaternion give a NaN pitch, like its roll and yaw
+    const double s_p = (double)a_p;
+    const double pitch = asin(s_p > 1.0 ? 1.0 : (s_p < -1.0 ? -1.0 : s_p));
     const double yaw = atan2((double)a_y, (double)b_y);
     float xs[NX];
     xs[0] = (float)roll;

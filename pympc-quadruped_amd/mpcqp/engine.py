@@ -263,7 +263,8 @@ class LinearMpc:
     # ---- the hot path's callers on the device (include/mpcqp.h) ----
 
     def set_planner(self, dt_control=0.001, gravity=9.81, max_pos_error=0.1):
-        """Planner constants (linear_mpc_configs.py:6,13; mpc.py:121)."""
+        """Planner constants (linear_mpc_configs.py:6,13; mpc.py:121).  A non-finite value, or a
+        negative dt_control / max_pos_error, raises and keeps the previous constants."""
         _lib.check(self._ctx, self.lib.mpcqp_set_planner(self._ctx, float(dt_control), float(gravity),
                                                          float(max_pos_error)), "mpcqp_set_planner")
 

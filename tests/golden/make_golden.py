@@ -19,6 +19,9 @@ SURVEY.md Appendix A), then:
                         _solve_mpc replaced by a recorder), quat2ZYXangle / quat2matrix
                         (kinematics.py:40-71) on float32 quaternions, and
                         LegController.update's stance branch (leg_controller.py:86-89)
+  planner_edges.npz     the same recording, 41 iterations at N = 10, at large attitudes,
+                        w < 0, vz != 0, negative and sub-threshold velocities and all four
+                        branches of the position clamp (--planner-edges)
 
   formulation_full_N{N}.npz  the same for full (non-diagonal) Q and R (--full N): leg-block R
                         at N = 10 / 16, an R coupling every pair of legs at N = 20 / 24 (the
@@ -27,6 +30,7 @@ SURVEY.md Appendix A), then:
 Usage:  python tests/golden/make_golden.py            (all horizons, subprocesses)
         python tests/golden/make_golden.py --horizon 10
         python tests/golden/make_golden.py --planner       (planner.npz only)
+        python tests/golden/make_golden.py --planner-edges (planner_edges.npz only)
 """
 import argparse
 import os
@@ -364,14 +368,125 @@ def gen_planner():
                         iterations_between_mpc=20, height=0.38)
 
 
+def gen_planner_edges():
+    """planner_edges.npz: gen_planner's recording at the inputs its mild sequence leaves out --
+    roll and pitch up to 1.2 rad, quaternions with a negative w, a body-frame command with
+    vz != 0 (the third column of R_base), negative and sub-threshold velocities, and base
+    positions that drive all four branches of the position clamp (mpc.py:129-137).
+
+    Every quaternion is normalised (math.asin raises past +-1) and every |velocity| stays 1e-3
+    away from the 0.2 / 0.1 compensation thresholds (mpc.py:143-146): exactly there NumPy 2.2
+    compares in float32 where the pinned 1.24 compares in float64, and the recording would
+    hold the wrong answer."""
+    import contextlib
+    import io
+    sys.path[:0] = [ROOT]
+    N = 10
+    LinearMpcConfig, robot_configs, mpc, gait = stub_reference(N)
+    import kinematics
+    B, T = 8, 41
+    members = [gait.Gait.TROTTING10, gait.Gait.PACING16, gait.Gait.STANDING, gait.Gait.TROTTING16,
+               gait.Gait.JUMPING16, gait.Gait.PACING10, gait.Gait.PACING16, gait.Gait.TROTTING10]
+    roll_a = np.array([1.2, -1.2, 0.3, -0.8, 1.0, 0.0, -1.2, 0.6])
+    pitch_a = np.array([0.1, 1.2, -1.2, 0.9, -1.0, 1.2, -0.3, -1.1])
+    yaw0 = np.array([0.0, 3.0, -3.1, 1.5, -1.6, 2.9, -0.5, 3.1])
+    yaw_d = np.array([0.01, 0.01, -0.01, 0.02, -0.02, 0.01, 0.0, 0.005])     # robots 1, 2, 5, 7 cross +-pi
+    v_body = np.array([[0.9, 0.2, 0.3], [-0.6, -0.4, -0.3], [0.4, 0.0, 0.5], [-0.3, 0.3, -0.2],
+                       [0.7, -0.2, 0.25], [0.0, 0.4, -0.4], [0.5, 0.1, 0.1], [-0.5, -0.1, 0.35]])
+    yaw_rate = np.array([0.5, -0.7, 0.2, -0.1, 0.8, 0.0, -0.4, 0.3])
+    vel_x = np.array([0.5, -0.5, 0.15, -0.15, 0.25, -0.25, 0.9, 0.05])        # + 0.02 sin t
+    vel_y = np.array([0.3, -0.3, 0.05, -0.05, 0.15, -0.15, 0.08, -0.4])       # + 0.01 cos t
+    p0 = np.array([[0.5, -0.4], [-0.5, 0.4], [0.05, 0.0], [-0.7, 0.6], [0.3, -0.05], [0.0, 0.3], [-0.2, -0.9],
+                   [0.9, 0.02]])
+    drift = np.array([[-0.012, 0.012], [0.012, -0.012], [0.008, 0.008], [0.004, -0.004], [-0.008, 0.01],
+                      [-0.008, -0.008], [0.01, 0.0], [0.0, -0.01]])
+    rng = np.random.default_rng(4041)
+    quat = np.zeros((B, T, 4), np.float32)
+    pos = np.zeros((B, T, 3), np.float32)
+    omega = np.zeros((B, T, 3), np.float32)
+    vel = np.zeros((B, T, 3), np.float32)
+    x0 = np.zeros((B, T, 13), np.float32)
+    rot = np.zeros((B, T, 3, 3), np.float32)
+    rpy = np.zeros((B, T, 3))
+    xref = np.zeros((B, 3, N * 13), np.float32)
+    table = np.zeros((B, 3, N * 4), np.float32)
+    pstate = np.zeros((B, 3, 5))
+    branches = set()
+    for b in range(B):
+        c = mpc.ModelPredictiveController(LinearMpcConfig, robot_configs.AliengoConfig)
+        assert c.iterations_between_mpc == 20 and c.horizon == N
+        k_mpc = 0
+        for t in range(T):
+            r = roll_a[b] * (0.9 + 0.1 * np.cos(0.3 * t))
+            p = pitch_a[b] * (0.9 + 0.1 * np.cos(0.2 * t))
+            y = yaw0[b] + yaw_d[b] * t
+            cr, sr, cp, sp, cy, sy = np.cos(r / 2), np.sin(r / 2), np.cos(p / 2), np.sin(p / 2), \
+                np.cos(y / 2), np.sin(y / 2)
+            q = np.array([cr * cp * cy + sr * sp * sy, sr * cp * cy - cr * sp * sy,
+                          cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy])
+            if b % 2:
+                q = -q                                           # the same attitude, w < 0
+            quat[b, t] = q.astype(np.float32)
+            assert abs(float(np.linalg.norm(quat[b, t].astype(np.float64))) - 1.0) < 1e-7
+            pos[b, t] = [p0[b, 0] + drift[b, 0] * t, p0[b, 1] + drift[b, 1] * t, 0.3 + 0.01 * np.sin(t)]
+            omega[b, t] = rng.uniform(-0.5, 0.5, 3)
+            vel[b, t] = [vel_x[b] + 0.02 * np.sin(t), vel_y[b] + 0.01 * np.cos(t), rng.uniform(-.1, .1)]
+            assert abs(abs(float(vel[b, t, 0])) - 0.2) >= 1e-3 and abs(abs(float(vel[b, t, 1])) - 0.1) >= 1e-3
+            rd = _PlanRobotData()
+            rd.quat_base = quat[b, t]
+            rd.pos_base = pos[b, t]
+            rd.ang_vel_base = omega[b, t]
+            rd.lin_vel_base = vel[b, t]
+            rd.R_base = kinematics.quat2matrix(quat[b, t])      # robot_data.py:75
+            rd.pos_base_feet = [np.zeros(3)] * 4
+            rot[b, t] = rd.R_base
+            rpy[b, t] = kinematics.quat2ZYXangle(quat[b, t])
+            members[b].set_iteration(c.iterations_between_mpc, t)
+            gt = members[b].get_gait_table()
+            rec = {}
+            c._solve_mpc = lambda ref, g, solver='drake', debug=False, rec=rec: \
+                (rec.update(ref=ref.copy(), g=np.array(g).copy()), np.zeros(12 * N))[1]
+            tick = t % c.iterations_between_mpc == 0
+            if tick:                                             # which clamp branch this tick takes
+                vd = rd.R_base @ v_body[b]
+                pre = (0.0, 0.0) if t == 0 else (c.xpos_base_desired + c.dt_control * vd[0],
+                                                 c.ypos_base_desired + c.dt_control * vd[1])
+                for ax, name in ((0, "x"), (1, "y")):
+                    d = pre[ax] - float(pos[b, t, ax])
+                    branches.add(name + ("+" if d > 0.1 else "-" if d < -0.1 else "0"))
+            c.update_robot_state(rd)
+            with contextlib.redirect_stdout(io.StringIO()):
+                c.update_mpc_if_needed(t, v_body[b].tolist(), float(yaw_rate[b]), gt)
+            x0[b, t] = c.current_state
+            if tick:
+                xref[b, k_mpc] = rec["ref"]
+                table[b, k_mpc] = rec["g"]
+                pstate[b, k_mpc] = [c.xpos_base_desired, c.ypos_base_desired, c.yaw_desired,
+                                    float(c.roll_init), float(c.pitch_init)]
+                k_mpc += 1
+    assert branches == {"x+", "x-", "x0", "y+", "y-", "y0"}, branches
+    assert (quat[:, :, 0] < 0).any() and np.abs(rpy[:, :, :2]).max() > 1.19
+    assert (np.abs(np.diff(rpy[:, :, 2], axis=1)) > 6.0).any()   # a yaw that wraps
+    gait_rec = np.array([[m.num_segment, *m.stance_offsets, *m.stance_durations] for m in members], np.int32)
+    np.savez_compressed(os.path.join(HERE, "planner_edges.npz"), quat=quat, pos=pos, omega=omega, vel=vel,
+                        v_body=v_body, yaw_rate=yaw_rate, x0=x0, rot=rot, rpy=rpy, xref=xref, table=table,
+                        plan_state=pstate, gait=gait_rec, horizon=N, iterations_between_mpc=20,
+                        height=float(c.com_height_des))
+    print(f"planner_edges.npz: B={B} T={T} N={N}, clamp branches {sorted(branches)}, "
+          f"|roll|,|pitch| up to {np.abs(rpy[:, :, :2]).max():.3f}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--horizon", type=int, default=0)
     ap.add_argument("--planner", action="store_true")
+    ap.add_argument("--planner-edges", action="store_true", help="planner_edges.npz only")
     ap.add_argument("--full", type=int, default=0, help="formulation_full_N{N}.npz only")
     a = ap.parse_args()
     if a.full:
         gen_full(a.full)
+    elif a.planner_edges:
+        gen_planner_edges()
     elif a.planner:
         gen_planner()
     elif a.horizon:

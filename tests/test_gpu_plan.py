@@ -108,7 +108,7 @@ def test_root_state_layout_is_the_same_computation():
         np.testing.assert_array_equal(u, v)
 
 
-@pytest.mark.parametrize("N", [10, 16, 20])
+@pytest.mark.parametrize("N", [10, 16, 20, 24, 32])
 def test_gait_tables_match_reference(N):
     """Gait.get_gait_table for every member at iterations 0..2*period (gait.py:76-100)."""
     from mpcqp._lib import PLAN_REFERENCE

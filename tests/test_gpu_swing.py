@@ -189,6 +189,102 @@ def test_tail_workgroup_and_masking(B):
         assert (out["mem"][B:] == -77.0).all()
 
 
+class _LegCall:
+    """mpcqp_leg_torques / _root_states through the C ABI for B robots on one tick: every
+    argument a valid device buffer (the outputs with 3 extra rows, all SENTINEL) unless
+    overridden, None = NULL."""
+    SENTINEL = -77.0
+
+    def __init__(self, eng, B, seed, tick=120):
+        import ctypes
+        from mpcqp.params import GAITS, gait_record
+        self.eng, self.B, self.ctypes = eng, B, ctypes
+        names = ["trot10"] + [k for k in GAITS if k != "trot10"]
+        inp = swing_ref.make_inputs(B, 1, seed=seed)
+        f4, f8 = torch.float32, torch.float64
+        self.t = {k: _dev(inp[k][0], f4) for k in ("quat", "pos", "vel", "pos_feet", "foot_pos_base", "foot_vel_base")}
+        self.t.update({k: _dev(inp[k], f4) for k in ("thighs", "jac", "u0")})
+        self.t.update(rot=None, rs=_dev(swing_ref.root_states(inp["quat"], inp["pos"], inp["vel"])[0], f4),
+                      vb=_dev(inp["v_body"], f8), yr=_dev(inp["yaw_rate"], f8),
+                      gait=_dev(np.stack([gait_record(names[b % len(names)]) for b in range(B)]), torch.int32),
+                      tick=torch.full((B,), tick, dtype=torch.int32, device=DEV))
+        self.fresh()
+
+    def fresh(self):
+        B = self.B
+        full = lambda *s: torch.full(s, self.SENTINEL, dtype=torch.float32, device=DEV)
+        self.out = dict(tau=full(B + 3, 12), swing_state=full(B + 3, 4), pos_target=full(B + 3, 4, 3),
+                        vel_target=full(B + 3, 4, 3))
+        self.mem = torch.full((B + 3, swing_ref.STRIDE), self.SENTINEL, dtype=torch.float64, device=DEV)
+        self.mem[:B] = 0.0
+
+    def __call__(self, root=False, batch=None, flags=0, ibm=20, **kw):
+        a = dict(self.t, mem=self.mem, **self.out)
+        a.update(kw)
+        ptr = lambda x: None if x is None else self.ctypes.c_void_p(x.data_ptr())
+        tail = [ptr(a[k]) for k in ("vb", "yr", "gait", "thighs", "pos_feet", "foot_pos_base", "foot_vel_base", "jac",
+                                    "u0", "mem", "tau", "swing_state", "pos_target", "vel_target")]
+        lib, ctx, batch = self.eng.lib, self.eng._ctx, self.B if batch is None else batch
+        if root:
+            return lib.mpcqp_leg_torques_root_states(ctx, batch, flags, ptr(a["tick"]), ibm, ptr(a["rs"]), *tail, None)
+        return lib.mpcqp_leg_torques(ctx, batch, flags, ptr(a["tick"]), ibm, *(ptr(a[k]) for k in ("quat", "pos", "vel", "rot")),
+                                     *tail, None)
+
+    def read(self):
+        torch.cuda.synchronize()
+        return dict({k: v.cpu().numpy() for k, v in self.out.items()}, mem=self.mem.cpu().numpy())
+
+
+def test_argument_errors():
+    """Every MPCQP_ERR_ARG branch of the leg-torque launch, each with its word in
+    mpcqp_last_error, B = 5; batch = 0 is a successful no-op; a refused call runs nothing."""
+    from mpcqp import _lib
+    eng = _engine()
+    c = _LegCall(eng, 5, seed=51)
+    odd = torch.zeros((5 * swing_ref.STRIDE + 1,), dtype=torch.float64, device=DEV)[1:]      # 8 bytes off a 16-byte line
+    assert odd.data_ptr() % 16 == 8
+    required = ("tick", "quat", "pos", "vel", "vb", "yr", "gait", "thighs", "pos_feet", "foot_pos_base", "foot_vel_base",
+                "jac", "u0", "mem", "tau")
+    refused = [(dict(batch=-1), "batch"), (dict(batch=-1, root=True), "batch"), (dict(flags=1), "flags"),
+               (dict(flags=2, root=True), "flags"), (dict(ibm=0), "iterations_between_mpc"),
+               (dict(ibm=-20, root=True), "iterations_between_mpc"), (dict(mem=odd), "aligned"),
+               (dict(mem=odd, root=True), "aligned"), (dict(rs=None, root=True), "null")]
+    refused += [({k: None}, "null") for k in required]
+    refused += [({k: None, "root": True}, "null") for k in required if k not in ("quat", "pos", "vel")]
+    for kw, word in refused:
+        assert c(**kw) == _lib.ERR_ARG, kw
+        assert word in eng.lib.mpcqp_last_error(eng._ctx).decode(), (kw, eng.lib.mpcqp_last_error(eng._ctx))
+    assert c(batch=0) == 0 and c(batch=0, root=True) == 0 and c(batch=0, quat=None, tau=None) == 0
+    o = c.read()
+    assert all((o[k] == c.SENTINEL).all() for k in c.out) and (o["mem"][:5] == 0).all() and (o["mem"][5:] == c.SENTINEL).all()
+    assert c() == 0                                               # the same buffers serve a good call
+    o = c.read()
+    assert all((o[k][:5] != c.SENTINEL).all() and (o[k][5:] == c.SENTINEL).all() for k in c.out)
+    assert (o["mem"][:5] != 0).any() and (o["mem"][5:] == c.SENTINEL).all()
+
+
+@pytest.mark.parametrize("layout", ["split", "root"])
+def test_nullable_outputs_absent(layout):
+    """swing_state, pos_target and vel_target NULL in turn, B = 5 on a tick with legs in swing:
+    tau, swing_mem and the other outputs are bitwise those of the full launch, and the absent
+    buffer keeps its sentinel."""
+    eng = _engine()
+    c = _LegCall(eng, 5, seed=52)
+    root = layout == "root"
+    assert c(root=root) == 0
+    want = c.read()
+    assert (want["swing_state"][:5] > 0).any() and (want["swing_state"][:5] == 0).any()
+    for skip in ("swing_state", "pos_target", "vel_target"):
+        c.fresh()
+        absent = c.out[skip]
+        assert c(root=root, **{skip: None}) == 0
+        got = c.read()
+        assert (got[skip] == c.SENTINEL).all() and absent is c.out[skip], skip
+        for k in want:
+            if k != skip:
+                assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), (skip, k)
+
+
 def test_reference_defaults_two_periods():
     """iterations_between_mpc = 20, TROTTING10, B = 3 with different per-robot tick
     offsets, 420 ticks (two full periods and a bit): every leg lifts off, lands and
