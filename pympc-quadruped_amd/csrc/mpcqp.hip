@@ -341,6 +341,9 @@ __device__ __forceinline__ int wave_argmin_f32(double v, double& vmin_out) {
   return l;
 }
 
+// class 64's setup-priority table (solve_robot): one u64 per CU, indexed by XCC_ID and the
+// CU / SH / SE fields of HW_ID (12 bits)
+constexpr int kPrioTab = 4096;
 #include "mpcqp_form.h"
 #include "mpcqp_combo_asm.h"
 #include "mpcqp_solve.h"
@@ -486,18 +489,26 @@ static_assert(ipm_within_slots<16, false, true>() && ipm_within_slots<16, true, 
 // Class NV = 64: one 2-wave workgroup per robot of the batch.  Robots with more
 // than 64 stance variables are appended to `queue` (when given) for class 96, those
 // with more than 96 to `queue_big` (when given) for class 128.
-template <bool FULL>
+// PRIO: the instantiation with the setup priority (solve_robot), for a batch the chip holds at
+// once; without it the kernel has none of that code and ignores its last two arguments.
+template <bool FULL, bool PRIO = false>
 __global__ __launch_bounds__(Cfg<64>::NT) __attribute__((amdgpu_waves_per_eu(2, Cfg<64>::NW))) void mpcqp_kernel_64(
     KParams P, int B, const float* __restrict__ x0g, const float* __restrict__ xrefg,
     const float* __restrict__ contactg, const float* __restrict__ feetg, const float* __restrict__ robotg,
     float* __restrict__ u0g, float* __restrict__ Ug, int* __restrict__ statusg, int* __restrict__ itersg,
-    int* __restrict__ queue, int* __restrict__ queue_big, int* __restrict__ queue_ipm, const int* __restrict__ perm) {
+    int* __restrict__ queue, int* __restrict__ queue_big, int* __restrict__ queue_ipm, const int* __restrict__ perm,
+    unsigned long long* __restrict__ prio_tab, unsigned prio_epoch) {
   if ((int)blockIdx.x >= B) return;
   int b = xcd_robot(blockIdx.x, B);
   if (perm) b = uni(perm[b]);   // the dispatch order (mpcqp_order_kernel, mode 0)
+  // the setup priority's value (solve_robot): the dispatch order's key under this launch's epoch
+  // (non-negative floats order as their bits)
+  unsigned long long prio_val = 0ull;
+  if constexpr (PRIO)
+    prio_val = ((unsigned long long)prio_epoch << 32) | __float_as_uint(order_key(x0g, xrefg, P.N, b));
   __shared__ SharedT<64> sm;
-  solve_robot<64, FULL>(P, b, sm, x0g, xrefg, contactg, feetg, robotg, u0g, Ug, statusg, itersg, queue, queue_big,
-                  queue_ipm);
+  solve_robot<64, FULL, PRIO>(P, b, sm, x0g, xrefg, contactg, feetg, robotg, u0g, Ug, statusg, itersg, queue, queue_big,
+                  queue_ipm, prio_tab, prio_val);
 }
 
 // Class NV = 96: one 6-wave workgroup (4 x 6 register tiles) per robot queued by
@@ -663,6 +674,11 @@ struct mpcqp_ctx {
   int ncu;
   std::vector<QueueSet> queues;
   unsigned long long use_clock;
+  // class 64's setup-priority table (kPrioTab u64, solve_robot) and the launch epoch its entries
+  // carry: a launch's entries beat every earlier launch's, so the table is cleared only at
+  // creation and when the 32-bit epoch wraps
+  unsigned long long* prio_tab;
+  unsigned prio_epoch;
   // the interior-point class's global slots (Riccati S_k; at N <= 16 also M_k, M_k^T and the
   // saved iterate): kIpmPerCU per CU, one pool for every stream of the context (the slots in
   // use never exceed the class's resident workgroups, whichever launches they belong to),
@@ -852,6 +868,22 @@ int mpcqp_create(const mpcqp_params* p, int32_t device, mpcqp_ctx** out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->ncu = prop.multiProcessorCount;
   if (ctx->ncu <= 0) ctx->ncu = 256;
+  ctx->prio_tab = nullptr;
+  ctx->prio_epoch = 0;
+  {
+    DeviceScope dev(device);
+    if (!dev.ok || hipMalloc(&ctx->prio_tab, sizeof(unsigned long long) * kPrioTab) != hipSuccess) {
+      delete ctx;
+      return MPCQP_ERR_ALLOC;
+    }
+    // cleared and waited for, so a first launch on any stream finds it cleared
+    if (hipMemsetAsync(ctx->prio_tab, 0, sizeof(unsigned long long) * kPrioTab, nullptr) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+      (void)hipFree(ctx->prio_tab);
+      delete ctx;
+      return MPCQP_ERR_HIP;
+    }
+  }
   *out = ctx;
   return MPCQP_OK;
 }
@@ -1024,9 +1056,20 @@ int mpcqp_solve(mpcqp_ctx* ctx, int32_t batch, const float* x0, const float* xre
     if (e != hipSuccess) return failed(set_err(ctx, MPCQP_ERR_HIP, std::string("launch (order): ") + hipGetErrorString(e)));
   }
   if (first == 0) {
-    hipLaunchKernelGGL(full ? mpcqp_kernel_64<true> : mpcqp_kernel_64<false>, dim3(batch), dim3(Cfg<64>::NT),
-                       kDiagLds, st, kp, (int)batch, x0, xref, contact,
-                       feet, robot, u0, U, (int*)status, (int*)iters, q1, q2, q3, perm);
+    // the setup priority (solve_robot) only for a batch the chip holds at once, whose launch lasts
+    // as long as its slowest robot; a batch that queues on the CUs is throughput-bound, and there
+    // the raised robots' gain did not cover their CU-mates' loss (config 3 -0.2 to -0.5 %, measured)
+    const bool prio = batch <= resident;
+    if (prio && ++ctx->prio_epoch == 0) {   // the epoch wrapped: earlier entries would win for ever
+      if (hipMemsetAsync(ctx->prio_tab, 0, sizeof(unsigned long long) * kPrioTab, st) != hipSuccess)
+        return failed(set_err(ctx, MPCQP_ERR_HIP, "priority table reset failed"));
+      ctx->prio_epoch = 1;
+    }
+    hipLaunchKernelGGL(prio ? (full ? mpcqp_kernel_64<true, true> : mpcqp_kernel_64<false, true>)
+                            : (full ? mpcqp_kernel_64<true> : mpcqp_kernel_64<false>),
+                       dim3(batch), dim3(Cfg<64>::NT), kDiagLds, st, kp, (int)batch, x0, xref, contact,
+                       feet, robot, u0, U, (int*)status, (int*)iters, q1, q2, q3, perm,
+                       prio ? ctx->prio_tab : (unsigned long long*)nullptr, ctx->prio_epoch);
     e = hipGetLastError();
     if (e != hipSuccess) return failed(set_err(ctx, MPCQP_ERR_HIP, std::string("launch: ") + hipGetErrorString(e)));
     if ((fe = fork_ipm()) != MPCQP_OK) return failed(fe);
@@ -1415,6 +1458,7 @@ int mpcqp_destroy(mpcqp_ctx* ctx) {
     // (a recorded stream may already have been destroyed by the caller)
     for (auto& q : ctx->queues) release_set(q);
     if (ctx->sscratch) (void)hipFree(ctx->sscratch);
+    if (ctx->prio_tab) (void)hipFree(ctx->prio_tab);
     if (ctx->wdev) (void)hipFree(ctx->wdev);
     for (double* o : ctx->retired) (void)hipFree(o);
   }

@@ -302,8 +302,16 @@ __device__ __forceinline__ void form_weights(const KParams& P, F& f, FormY& fy, 
 // inv(I_w) -> K, G passes through LDS inside wave 0 (wave fences, no workgroup barrier) while
 // wave 1, which needs none of it, builds the cone rows and the horizon suffix sums: ONE
 // workgroup barrier between the staged inputs and the Ya/Yb loop.
-template <int NT, bool SPLIT = false, class F, class MT>
-__device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT& mt, int N, int tid) {
+// `pre_barrier`: work of the caller's that needs none of this, run by every thread just ahead
+// of the workgroup barrier in front of Ya/Yb, where wave 1 of the split setup waits for wave
+// 0's chain (class 64 reads its setup-priority entry there); with full weights, at the start
+// of their model.
+struct FormNoHook {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <int NT, bool SPLIT = false, class F, class MT, class PB = FormNoHook>
+__device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT& mt, int N, int tid,
+                                           PB pre_barrier = PB()) {
   static_assert(!SPLIT || NT == 2 * LANES, "the split setup is laid out for two waves");
   constexpr int CS = SPLIT ? LANES : NT;   // threads the chain's syncs cover
   // first thread of the suffix sums (13 threads) and of the cone rows (18 threads)
@@ -400,6 +408,7 @@ __device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT
     if (k18 == 0) mt.fz0_implied = mu > 0.0;
   }
   if (P.wfull) {
+    pre_barrier();
     form_model_full<NT>(P, f, fy, N, tid);
     return;
   }
@@ -425,6 +434,7 @@ __device__ __forceinline__ void form_model(const KParams& P, F& f, FormY& fy, MT
       if (sc < 6) f.E1[t][sc] = e1;
     }
   }
+  pre_barrier();
   fsync<NT>();
   // ---- Ya, Yb (12 x 12 each)
   {

@@ -92,6 +92,7 @@ struct alignas(16) SharedT {
   alignas(16) double yv[Cfg<NV>::VEC];
   double wmax[Cfg<NV>::NW];
   int choice;   // classes 64 / 96 (split choice): wave 1's published {pass tag, p2 + 1, p + 1}
+  int prio;     // class 64: wave 1's setup-priority decision (in the struct's tail padding)
 };
 // the formulation scratch must not grow the H copy's union (class 64: 4 robots per CU)
 static_assert(sizeof(FormArea<64>) <= sizeof(double) * 64 * 64, "formulation scratch exceeds the H copy");
@@ -186,14 +187,16 @@ __device__ __forceinline__ void write_empty_t(int b, int tid, int N, int code, f
 // One robot.  A robot exceeding NV is appended to `queue` (when given) for the
 // next capacity class -- or to `queue_big` / `queue_ipm` for the ones after, when
 // it exceeds those too -- otherwise reported MPCQP_STATUS_TOO_LARGE.
-template <int NV, bool FULL>
+template <int NV, bool FULL, bool PRIO = false>
 __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>& sm, const float* __restrict__ x0g,
                                             const float* __restrict__ xrefg, const float* __restrict__ contactg,
                                             const float* __restrict__ feetg, const float* __restrict__ robotg,
                                             float* __restrict__ u0g, float* __restrict__ Ug, int* __restrict__ statusg,
                                             int* __restrict__ itersg, int* __restrict__ queue,
                                             int* __restrict__ queue_big = nullptr,
-                                            int* __restrict__ queue_ipm = nullptr) {
+                                            int* __restrict__ queue_ipm = nullptr,
+                                            unsigned long long* __restrict__ prio_tab = nullptr,
+                                            unsigned long long prio_val = 0ull) {
   using C = Cfg<NV>;
   constexpr int NT = C::NT, TCN = C::TCN, CPL = C::CPL, VPL = C::VPL, RPW = C::RPW, TW = C::TW;
   const int tid = threadIdx.x;
@@ -243,6 +246,32 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
     return;
   }
   SUBSTAMP(0);
+  // Class 64: the heaviest robot of each CU takes the SIMDs first during the H tile and the
+  // sweep.  A launch lasts as long as its slowest robot, whose CU-mates mostly finish early:
+  // two waves of a SIMD in the same f64 phase get half the pipe each, and the robot with no
+  // slack should not be the one to wait.  Each workgroup publishes (launch epoch, predicted
+  // cost) -- prio_val, the dispatch order's key under the launch's epoch -- by an atomic max on
+  // its CU's entry of the context's table, reads the entry back ahead of the H tile, and runs
+  // at priority 3 until the end of the sweep when the entry is its own.  The epoch makes
+  // earlier launches' entries lose, so the table is never cleared.  Wave 1 does both memory
+  // operations: it waits for wave 0's model chain anyway, so the atomic and the load (issued
+  // through form_model's pre_barrier, ~2 k cycles after the CU-mates, which start within ~1 us,
+  // have published) cost wave 0 nothing; the decision reaches wave 0 through sm.prio behind the
+  // Ya/Yb barrier.  This is a schedule, never a result: a workgroup that reads before its
+  // mates have written, a hardware-id field that means something else (the index is masked to
+  // the table), launches of two streams sharing the table or a replayed graph's repeated epoch
+  // only raise the wrong robot, or none.  (PRIO: a batch that queues on the CUs is launched
+  // without any of this, mpcqp_solve.)
+  unsigned long long* prio_slot = nullptr;   // wave 1 only
+  static_assert(!PRIO || NV == 64, "the setup priority is class 64's");
+  if constexpr (PRIO) {
+    if (prio_tab && wave == 1) {
+      const unsigned hw = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_ID: CU, SH, SE at bits 8..15
+      const unsigned xcc = (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);      // XCC_ID
+      prio_slot = prio_tab + ((((xcc & 15u) << 8) | ((hw >> 8) & 0xffu)) & (unsigned)(kPrioTab - 1));
+      if (lane == 0) (void)__hip_atomic_fetch_max(prio_slot, prio_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
   // split: every wave counts the stance foot-steps for itself (no barrier); wave 0 writes the
   // lists, which wave 1 reads behind form_model's barrier
   int S;
@@ -270,7 +299,15 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
 
   // ------------------------------------------------ formulation (mpcqp_form.h)
   SUBSTAMP(1);
-  form_model<NT, kSplitSetup>(P, smf, smfy, sm.mt, N, tid);
+  unsigned long long prio_seen = ~0ull;
+  if constexpr (PRIO) {
+    // the CU's entry back (wave 1: every lane the same address), waited for at form_model's barrier
+    form_model<NT, kSplitSetup>(P, smf, smfy, sm.mt, N, tid, [&] {
+      if (prio_slot) prio_seen = __hip_atomic_load(prio_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
+  } else {
+    form_model<NT, kSplitSetup>(P, smf, smfy, sm.mt, N, tid);
+  }
   SUBSTAMP(2);
   if constexpr (kSplitSetup) {
     // g needs K, G and the suffix sums, all behind form_model's barrier, not its Ya/Yb: wave 1
@@ -279,13 +316,21 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
       const int a = tid - (NT - NV);
       sm.gv[a] = a < n ? form_g(P, smf, sm.mt, a) : 0.0;
     }
-    fsync<NT>();   // Ya/Yb, g
+    if constexpr (PRIO) {
+      if (prio_slot && lane == 0) sm.prio = prio_seen == prio_val;
+    }
+    fsync<NT>();   // Ya/Yb, g, prio
   } else {
     fill_mt_tab();
     fsync<NT>();
     if (tid < NV) sm.gv[tid] = tid < n ? form_g(P, smf, sm.mt, tid) : 0.0;
   }
   STAMP(1);
+  bool prio_raised = false;
+  if constexpr (PRIO) {
+    prio_raised = prio_tab && uni(sm.prio) != 0;
+    if (prio_raised) __builtin_amdgcn_s_setprio(3);
+  }
 
   // row `r` of the lane's H tile (identity padding beyond n); cj / cc: the tile
   // columns' foot-step horizon step and input column
@@ -523,6 +568,9 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
       if ((unsigned)(c - c0) < 3u) sm.wb[wi + c] = W[r][c];
   }
   STAMP(3);
+  if constexpr (PRIO) {
+    if (prio_raised) __builtin_amdgcn_s_setprio(0);   // the setup priority ends with the sweep
+  }
 
   // unconstrained minimiser x = -W g
   {
@@ -1210,8 +1258,8 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
 
 #ifdef MPCQP_STAMPS
   // stamps build: U is a diagnostic buffer of kStampU64 u64 per robot (tools/phase_stamps.py):
-  // [0, 7) phase stamps, 7 / 8 chip-wide start / end (s_memrealtime), [9, 12) sub-stamps, [16, 24) each wave's HW_ID,
-  // [32 + 24 w, 56 + 24 w) wave w's section accumulators and event counters (lane k: section k)
+  // [0, 7) phase stamps, 7 / 8 chip-wide start / end (s_memrealtime), [9, 12) sub-stamps, 12 the setup-priority flag,
+  // [16, 24) each wave's HW_ID, [32 + 24 w, 56 + 24 w) wave w's section accumulators and event counters (lane k: section k)
   if (Ug) {
     unsigned long long* dst = (unsigned long long*)Ug + (size_t)b * kStampU64;
     if (tid == 0) {
@@ -1219,6 +1267,7 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
       dst[7] = rt0_;
       dst[8] = __builtin_amdgcn_s_memrealtime();
       for (int i = 0; i < 3; ++i) dst[9 + i] = substamps_[i];
+      dst[12] = prio_raised ? 1ull : 0ull;   // class 64: ran its H tile and sweep at raised priority
     }
     if (lane < 24) dst[32 + 24 * wave + lane] = secacc_;
     if (lane == 0)   // SIMD, CU, SE; XCC_ID; workgroup id

@@ -3,7 +3,8 @@
 Uses a separately built libmpcqp_stamps.so (-DMPCQP_STAMPS, `python tools/phase_stamps.py build`)
 whose kernels write, per robot, into the U buffer taken as 256 u64 slots (mpcqp_solve.h):
 [0, 7) phase stamps, 7 / 8 chip-wide start / end (s_memrealtime, 100 MHz), [9, 12) sub-stamps of
-the first phase (after staging, after the stance list, after the model), [16, 24) each wave's
+the first phase (after staging, after the stance list, after the model), 12 class 64's
+setup-priority flag (the robot ran its H tile and sweep at raised priority), [16, 24) each wave's
 HW_ID, [32 + 24 w, 56 + 24 w) wave w's section accumulators (lane k: section k) and event
 counters.  The shipped library executes no stamp.  Prints median / max cycles per phase and, per
 wave, the active set's cycles per iteration by section.
@@ -87,6 +88,10 @@ def main():
             print(f"    {name:24s} median {np.median(v):9.0f}  max {v.max():9.0f} cycles")
     setup = ts[:, 3] - ts[:, 0]
     print(f"  {'setup (first three)':26s} median {np.median(setup):9.0f}  max {setup.max():9.0f} cycles")
+    raised = slots[:, 12] != 0   # class 64's setup priority (the heaviest robot of each CU)
+    if raised.any() and not raised.all():
+        print(f"  setup at raised priority: {int(raised.sum())} robots, median {np.median(setup[raised]):.0f} cycles; "
+              f"the others' median {np.median(setup[~raised]):.0f}")
     tot = ts[:, 6] - ts[:, 0]
     print(f"  {'total':26s} median {np.median(tot):9.0f}  max {tot.max():9.0f}")
     rt = slots[:, 7:9]
