@@ -247,8 +247,10 @@ int mpcqp_stance_torques(mpcqp_ctx* ctx, int32_t batch, const float* jac, const 
  * read: it can be captured into a HIP graph (tick lives on the device, so a replay sees
  * fresh counters).  A leg swings while its swing state is > 0 and is in stance otherwise;
  * the decision is taken in integer arithmetic on tick % (iterations_between_mpc * period).
- * A swing offset past the period wraps per leg, and a leg whose stance fills the period
- * never swings (deviations).
+ * A swing offset past the period wraps per leg -- a negative stance offset wraps the same
+ * way, and swing_state is (ticks into the swing) / (ticks per swing) for either -- and a leg
+ * whose stance fills the period never swings, nor does any leg of a record with period <= 0:
+ * such a leg is in stance and its swing_mem is not written (deviations).
  *
  *   flags        0 (reserved)
  *   tick         [B]     int32: each robot's control-iteration counter (iter_counter,

@@ -53,7 +53,8 @@ __host__ __device__ inline bool swing_counts(int tick, int ibm, int period, int 
 // (gait.py:104-106 subtracts 1 from all four legs: DESIGN.md, deviations).  A leg whose
 // stance fills the period never swings (the reference's 0 / 0 there: DESIGN.md), nor does
 // a malformed record (period <= 0, ibm <= 0).  *value = swing_state, the reference's
-// float division on its float32 phase.
+// float division on its float32 phase; it is cs / nsw to the rounding of that phase for
+// every offset, negative ones and ones past the period included.
 __host__ __device__ inline int swing_decide(int tick, int ibm, int period, int off, int dur, double* value) {
 #pragma clang fp contract(off)
   *value = 0.0;
@@ -62,8 +63,12 @@ __host__ __device__ inline int swing_decide(int tick, int ibm, int period, int o
   if (cs == 0 || cs > nsw) return SWING_STANCE;
   const long long span = (long long)ibm * period;
   const float phase = (float)((double)c / (double)span);   // phase_state is a float32 array
+  // the swing offset as a fraction of the period, brought into [0, 1] as the integers above bring
+  // cs into [0, span): (1, 2] loses 1 as in the reference (an offset of exactly 1 stays), anything
+  // further out -- a negative stance offset, one past twice the period -- its whole periods
   double so = (double)off / (double)period + (double)dur / (double)period;
-  if (so > 1.0) so -= 1.0;
+  if (so > 1.0) so -= ceil(so) - 1.0;
+  if (so < 0.0) so -= floor(so);
   const double sd = 1.0 - (double)dur / (double)period;
   double s = (double)phase - so;
   if (s < 0.0) s += 1.0;

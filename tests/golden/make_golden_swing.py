@@ -23,7 +23,20 @@ Gait.STANDING's swing state is 0 / 0 = nan at phase 0 (gait.py:116-119: swing du
 targets; the fixture records that as the reference produced it, the tests skip those
 entries (DESIGN.md, deviations).
 
-Usage:  python tests/golden/make_golden_swing.py
+A second entry, tests/golden/swing_edges.npz, is the same run where swing.npz cannot
+see a mistake: full, non-symmetric Kp_swing / Kd_swing (nine distinct entries each, two
+gain groups), thigh positions with the z a hip angle gives them (per leg different), a
+commanded body velocity with a z part, wider yaw rates and base tilts, and
+LinearMpcConfig.gravity, LinearMpcConfig.dt_control and AliengoConfig.swing_height off
+their defaults (the generators and the Gait members read them when they are constructed,
+so they are set first); iteration_between_mpc = 2, every tick of two periods of the
+16-segment gaits plus 4, the generators' state at every 2nd tick.  touchdown_z and
+vel_gain are literals in the reference (swing_foot_trajectory_generator.py:116,120) and
+stay what they are.  Each entry runs in a process of its own, because the Gait members
+capture the constants when the module is imported.
+
+Usage:  python tests/golden/make_golden_swing.py            (both files)
+        python tests/golden/make_golden_swing.py edges      (one of: swing, edges)
 """
 import os
 import sys
@@ -36,9 +49,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from make_golden import REF, stub_reference  # noqa: E402
 
-IBM = 4
-T = 136          # two periods of the 16-segment gaits plus 8 ticks
-CHECK = 8        # the generators' private state is recorded every CHECK-th tick
+# ibm: iteration_between_mpc; T: two periods of the 16-segment gaits plus a few ticks; check:
+# the generators' private state is recorded every check-th tick
+ENTRIES = {
+    "swing": dict(out="swing.npz", ibm=4, T=136, check=8, seed=31337, edges=False),
+    "edges": dict(out="swing_edges.npz", ibm=2, T=68, check=2, seed=27182, edges=True,
+                  dt_control=0.002, gravity=3.72, swing_height=0.07),
+}
+# the two gain groups of the edges entry (robots 0-2, robots 3-5)
+KP_EDGES = np.array([[[700.0, 92.0, -110.0], [-80.0, 640.0, 130.0], [150.0, -88.0, 760.0]],
+                     [[200.0, -35.0, 28.0], [42.0, 230.0, -31.0], [-26.0, 55.0, 170.0]]])
+KD_EDGES = np.array([[[20.0, 3.5, -2.5], [-4.0, 17.0, 2.4], [3.1, -2.8, 23.0]],
+                     [[12.0, -1.9, 2.6], [1.5, 14.0, -3.3], [-2.1, 1.7, 9.0]]])
 
 
 class _Curve:
@@ -66,11 +88,23 @@ class _RobotData:
     LegController.update read (robot_data.py:59-190), set directly."""
 
 
-def main():
+def _signed(rng, lo, hi, size=None):
+    """Magnitudes in [lo, hi] with a random sign: none of them near 0."""
+    return rng.uniform(lo, hi, size) * rng.choice([-1.0, 1.0], size)
+
+
+def main(entry):
+    cfg = ENTRIES[entry]
+    IBM, T, CHECK, edges = cfg["ibm"], cfg["T"], cfg["check"], cfg["edges"]
     sys.path.insert(0, f"{REF}/config")
     import linear_mpc_configs
     linear_mpc_configs.LinearMpcConfig.iteration_between_mpc = IBM
+    for k in ("dt_control", "gravity"):
+        if k in cfg:
+            setattr(linear_mpc_configs.LinearMpcConfig, k, cfg[k])
     LinearMpcConfig, robot_configs, mpc, gait = stub_reference(16)
+    if "swing_height" in cfg:
+        robot_configs.AliengoConfig.swing_height = cfg["swing_height"]
     sys.modules["pydrake.all"].PiecewisePolynomial = PiecewisePolynomial
     try:
         import matplotlib.pyplot  # noqa: F401
@@ -84,7 +118,7 @@ def main():
 
     members = list(gait.Gait)
     B = len(members)
-    rng = np.random.default_rng(31337)
+    rng = np.random.default_rng(cfg["seed"])
     f32 = np.float32
     quat = np.zeros((B, T, 4), f32)
     pos = np.zeros((B, T, 3), f32)
@@ -97,8 +131,11 @@ def main():
     u0 = rng.uniform(-40, 120, (B, 12)).astype(f32)
     v_body = np.zeros((B, 3))
     yaw_rate = np.zeros(B)
-    kp = np.array([700.0] * 3 + [200.0] * 3)
-    kd = np.full(B, 20.0)
+    if edges:
+        kp, kd = np.repeat(KP_EDGES, 3, axis=0), np.repeat(KD_EDGES, 3, axis=0)      # [B,3,3]
+    else:
+        kp = np.array([700.0] * 3 + [200.0] * 3)
+        kd = np.full(B, 20.0)
     swing_state = np.zeros((B, T, 4))
     pos_target = np.zeros((B, T, 4, 3))
     vel_target = np.zeros((B, T, 4, 3))
@@ -117,7 +154,16 @@ def main():
         rpy0 = np.array([rng.uniform(-0.15, 0.15), rng.uniform(-0.15, 0.15), rng.uniform(-3.1, 3.1)])
         p0 = np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), 0.38])
         ph = rng.uniform(0, 6.28, (4, 3))
-        lc = leg_controller.LegController(np.diag([kp[b]] * 3), np.diag([kd[b]] * 3))
+        if edges:
+            # what BatchedController.step feeds and swing.npz leaves at zero or small: thigh z =
+            # d sin(q_hip), a commanded z velocity, a yaw rate and a tilt well away from 0
+            v_body[b][2] = _signed(rng, 0.3, 0.6)
+            yaw_rate[b] = _signed(rng, 1.0, 2.5)
+            thighs[b, :, 2] = _signed(rng, 0.02, 0.08, 4)
+            rpy0[:2] = _signed(rng, 0.2, 0.35, 2)
+            lc = leg_controller.LegController(kp[b].copy(), kd[b].copy())
+        else:
+            lc = leg_controller.LegController(np.diag([kp[b]] * 3), np.diag([kd[b]] * 3))
         gens = [sftg.SwingFootTrajectoryGenerator(leg) for leg in range(4)]
         jv = np.zeros((4, 3, 18), f32)
         for leg in range(4):
@@ -171,7 +217,7 @@ def main():
                     ck_init[b, k, leg] = np.asarray(getattr(g, priv + "footpos_init"), float).reshape(3)
                     ck_final[b, k, leg] = np.asarray(getattr(g, priv + "footpos_final"), float).reshape(3)
     gait_rec = np.array([[m.num_segment, *m.stance_offsets, *m.stance_durations] for m in members], np.int32)
-    out = os.path.join(HERE, "swing.npz")
+    out = os.path.join(HERE, cfg["out"])
     np.savez_compressed(
         out, member=np.array([m._name_ for m in members]), gait=gait_rec, iterations_between_mpc=IBM,
         dt_control=LinearMpcConfig.dt_control, gravity=float(LinearMpcConfig.gravity),
@@ -189,4 +235,9 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1:
+        main(sys.argv[1])
+    else:
+        import subprocess
+        for name in ENTRIES:
+            subprocess.run([sys.executable, os.path.abspath(__file__), name], check=True)

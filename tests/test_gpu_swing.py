@@ -24,7 +24,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import swing_ref  # noqa: E402
-from swing_ref import SwingRef, norm_err  # noqa: E402
+from swing_ref import norm_err, run_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +45,14 @@ def _engine(kp=700.0, kd=20.0, **kw):
     return eng
 
 
-def run_device(eng, inp, gait, ticks, ibm, layout="split", groups=None, pad=0, sentinel=-77.0, mem_every=0):
+def run_device(eng, inp, gait, ticks, ibm, layout="split", groups=None, pad=0, sentinel=-77.0, mem_every=0,
+               swing=None, mem0=None):
     """Run T ticks of B robots on the device.  inp: swing_ref.make_inputs-style arrays
     (per-tick [T,B,...] or per-robot [B,...]); ticks [T,B].  groups: [(slice, Kp, Kd)] launched
-    one after the other with their own gains (default: one launch per tick).  The output
-    buffers have `pad` extra rows filled with `sentinel`, returned too."""
+    one after the other with their own gains (default: one launch per tick) and the scalars
+    `swing` (set_swing keywords; default: set_swing's defaults).  The output buffers have
+    `pad` extra rows filled with `sentinel`, returned too.  mem0 [B,STRIDE]: the generator
+    state the run starts from (default: zeros)."""
     ticks = np.asarray(ticks, np.int32)
     T, B = ticks.shape
     f4, f8 = torch.float32, torch.float64
@@ -63,12 +66,12 @@ def run_device(eng, inp, gait, ticks, ibm, layout="split", groups=None, pad=0, s
     tau, ss = full(T, B + pad, 12), full(T, B + pad, 4)
     pt, vt = full(T, B + pad, 4, 3), full(T, B + pad, 4, 3)
     mem = full(B + pad, swing_ref.STRIDE, dt=f8)
-    mem[:B] = 0.0
+    mem[:B] = 0.0 if mem0 is None else _dev(mem0, f8).reshape(B, swing_ref.STRIDE)
     cks = []
     for t in range(T):
         for sl, kp, kd in (groups or [(slice(0, B), None, None)]):
             if kp is not None:
-                eng.set_swing(Kp=kp, Kd=kd)
+                eng.set_swing(Kp=kp, Kd=kd, **(swing or {}))
             kw = dict(root_states=rs[t, sl]) if layout == "root" else dict(
                 quat=per_tick["quat"][t, sl], pos=per_tick["pos"][t, sl], vel=per_tick["vel"][t, sl],
                 rot=per_tick["rot"][t, sl] if layout == "rot" else None)
@@ -84,21 +87,6 @@ def run_device(eng, inp, gait, ticks, ibm, layout="split", groups=None, pad=0, s
     if cks:
         out["ck_mem"] = torch.stack(cks, 1).cpu().numpy().reshape(B, len(cks), 4, 8)
     return out
-
-
-def run_ref(inp, gait, ticks, ibm, **kw):
-    """The same T ticks through swing_ref: arrays [T,B,...] and the final mem."""
-    ticks = np.asarray(ticks)
-    T, B = ticks.shape
-    ref = SwingRef(B, **kw)
-    outs = []
-    for t in range(T):
-        outs.append(ref.step(ticks[t], ibm, gait, inp["pos"][t], inp["vel"][t], inp["rot"][t], inp["v_body"],
-                             inp["yaw_rate"], inp["thighs"], inp["pos_feet"][t], inp["foot_pos_base"][t],
-                             inp["foot_vel_base"][t], inp["jac"], inp["u0"]))
-    o = {k: np.stack([x[k] for x in outs]) for k in outs[0]}
-    o["mem"] = ref.mem.reshape(B, swing_ref.STRIDE).copy()
-    return o
 
 
 def assert_matches_ref(out, ref, B, tag=""):
@@ -124,30 +112,19 @@ def fx():
 @pytest.fixture(scope="module")
 def fx_inputs(fx):
     """The fixture's inputs as [T,B,...] arrays, R_base by the float32 quat2matrix."""
-    B, T = fx["tau"].shape[:2]
-    tb = lambda a: np.ascontiguousarray(np.swapaxes(a, 0, 1))
-    inp = {k: tb(fx[k]) for k in ("quat", "pos", "vel", "pos_feet", "foot_pos_base", "foot_vel_base")}
-    inp["rot"] = swing_ref.quat2matrix_f32(inp["quat"].reshape(-1, 4)).reshape(T, B, 3, 3)
-    for k in ("v_body", "yaw_rate", "thighs", "jac", "u0"):
-        inp[k] = fx[k]
-    return inp
+    return swing_ref.fixture_inputs(fx)
 
 
-@pytest.mark.parametrize("layout", ["split", "root", "rot"])
-def test_fixture_sequence(fx, fx_inputs, layout):
-    """The reference's recorded run, B = 6, through both input layouts and once more with
-    R_base supplied: mask exact on every tick, first-swing flags exact at the checkpoints,
-    tau / targets / swing_state / checkpointed swing_mem within BOUND; stance entries
-    bitwise those of mpcqp_stance_torques on the same inputs."""
+def fixture_sequence_checks(fx, fx_inputs, layout, eng, groups, swing=None):
+    """A recorded run of the reference through one input layout: mask exact on every tick,
+    first-swing flags exact at the checkpoints, tau / targets / swing_state / checkpointed
+    swing_mem within BOUND; for "split" also the stance entries bitwise those of
+    mpcqp_stance_torques on the same inputs."""
     B, T = fx["tau"].shape[:2]
     ibm, every = int(fx["iterations_between_mpc"]), int(fx["check_every"])
-    eng = _engine(swing_height=float(fx["swing_height"]), touchdown_z=float(fx["touchdown_z"]),
-                  vel_gain=float(fx["vel_gain"]))
-    groups = [(slice(0, 3), float(fx["kp"][0]), float(fx["kd"][0])), (slice(3, 6), float(fx["kp"][3]),
-                                                                      float(fx["kd"][3]))]
-    assert (fx["kp"][:3] == fx["kp"][0]).all() and (fx["kp"][3:] == fx["kp"][3]).all()
     ticks = np.tile(np.arange(T)[:, None], (1, B))
-    out = run_device(eng, fx_inputs, fx["gait"], ticks, ibm, layout=layout, groups=groups, mem_every=every)
+    out = run_device(eng, fx_inputs, fx["gait"], ticks, ibm, layout=layout, groups=groups, mem_every=every,
+                     swing=swing)
     seq = {k: np.swapaxes(out[k], 0, 1) for k in ("tau", "swing_state", "pos_target", "vel_target")}
     seq["ck_mem"] = out["ck_mem"]
     errs = swing_ref.compare_fixture(fx, seq)          # asserts the mask and the flags
@@ -166,6 +143,20 @@ def test_fixture_sequence(fx, fx_inputs, layout):
     st = np.repeat(out["swing_state"] == 0, 3, axis=2)
     assert st.any() and (~st).any()
     assert np.array_equal(out["tau"][st].view(np.uint32), tau2.cpu().numpy()[st].view(np.uint32))
+
+
+@pytest.mark.parametrize("layout", ["split", "root", "rot"])
+def test_fixture_sequence(fx, fx_inputs, layout):
+    """The reference's recorded run, B = 6, through both input layouts and once more with
+    R_base supplied: mask exact on every tick, first-swing flags exact at the checkpoints,
+    tau / targets / swing_state / checkpointed swing_mem within BOUND; stance entries
+    bitwise those of mpcqp_stance_torques on the same inputs."""
+    eng = _engine(swing_height=float(fx["swing_height"]), touchdown_z=float(fx["touchdown_z"]),
+                  vel_gain=float(fx["vel_gain"]))
+    groups = [(slice(0, 3), float(fx["kp"][0]), float(fx["kd"][0])), (slice(3, 6), float(fx["kp"][3]),
+                                                                      float(fx["kd"][3]))]
+    assert (fx["kp"][:3] == fx["kp"][0]).all() and (fx["kp"][3:] == fx["kp"][3]).all()
+    fixture_sequence_checks(fx, fx_inputs, layout, eng, groups)
 
 
 @pytest.mark.parametrize("B", [1, 65, 257])

@@ -1,7 +1,10 @@
 """CPU: the swing half of the leg controller (mpcqp_leg_torques) without a GPU -- its
 ABI surface, the float64 restatement tests/swing_ref.py and the host-compiled per-leg
-header csrc/mpcqp_swing_leg.h, both against the reference's recorded run
-(tests/golden/swing.npz), and the curve's known answers.
+header csrc/mpcqp_swing_leg.h, both against the reference's two recorded runs
+(tests/golden/swing.npz, and swing_edges.npz with full gains, thigh z, commanded z
+velocity and constants off their defaults), the curve's known answers, the decision's
+integer edges, and that the inputs of tests/test_gpu_swing_edges.py can tell a wrong
+kernel from a right one.
 
 Measured here (norm-wise per robot, max over robots and quantities; printed by the two
 fixture tests): see CPU_BOUND below and the docstring of tests/test_gpu_swing.py."""
@@ -100,6 +103,11 @@ def fx():
 
 
 @pytest.fixture(scope="module")
+def fxe():
+    return swing_ref.load_fixture("swing_edges.npz")
+
+
+@pytest.fixture(scope="module")
 def leg(tmp_path_factory):
     d = tmp_path_factory.mktemp("swing")
     src, so = d / "shim.cpp", d / "libswing.so"
@@ -122,9 +130,12 @@ def _report(tag, errs):
     return worst
 
 
-def test_restatement_reproduces_the_reference_run(fx):
-    """swing_ref against swing.npz: the swing mask on every tick and the first-swing flags
-    at the checkpoints exactly, the values within CPU_BOUND."""
+def _gain3(k):
+    k = np.asarray(k, np.float64)
+    return np.ascontiguousarray(k if k.ndim == 2 else np.eye(3) * k)
+
+
+def _restatement_run(fx):
     B, T = fx["tau"].shape[:2]
     ibm, every = int(fx["iterations_between_mpc"]), int(fx["check_every"])
     ref = SwingRef(B, dt_control=float(fx["dt_control"]), gravity=float(fx["gravity"]),
@@ -139,12 +150,17 @@ def test_restatement_reproduces_the_reference_run(fx):
             seq[k][:, t] = o[k]
         if t % every == 0:
             seq["ck_mem"][:, t // every] = ref.mem
-    worst = _report("swing_ref vs swing.npz", swing_ref.compare_fixture(fx, seq))
+    return seq
+
+
+def test_restatement_reproduces_the_reference_run(fx):
+    """swing_ref against swing.npz: the swing mask on every tick and the first-swing flags
+    at the checkpoints exactly, the values within CPU_BOUND."""
+    worst = _report("swing_ref vs swing.npz", swing_ref.compare_fixture(fx, _restatement_run(fx)))
     assert worst < CPU_BOUND
 
 
-def test_host_compiled_header_reproduces_the_reference_run(fx, leg):
-    """csrc/mpcqp_swing_leg.h compiled with g++ and driven tick by tick: the same checks."""
+def _header_run(fx, leg):
     B, T = fx["tau"].shape[:2]
     ibm, every = int(fx["iterations_between_mpc"]), int(fx["check_every"])
     dp, fp, ip = leg.dp, leg.fp, leg.ip
@@ -154,7 +170,7 @@ def test_host_compiled_header_reproduces_the_reference_run(fx, leg):
     mem = np.zeros((B, 4, 8))
     tau, sv, pt, vt = np.zeros(3, np.float32), ctypes.c_double(), np.zeros(3), np.zeros(3)
     for b in range(B):
-        Kp, Kd = d(np.eye(3) * fx["kp"][b]), d(np.eye(3) * fx["kd"][b])
+        Kp, Kd = _gain3(fx["kp"][b]), _gain3(fx["kd"][b])
         gait = np.ascontiguousarray(fx["gait"][b], np.int32)
         vb = d(fx["v_body"][b])
         for t in range(T):
@@ -179,8 +195,97 @@ def test_host_compiled_header_reproduces_the_reference_run(fx, leg):
                 seq["vel_target"][b, t, l] = vt
             if t % every == 0:
                 seq["ck_mem"][b, t // every] = mem[b]
-    worst = _report("mpcqp_swing_leg.h (g++) vs swing.npz", swing_ref.compare_fixture(fx, seq))
+    return seq
+
+
+def test_host_compiled_header_reproduces_the_reference_run(fx, leg):
+    """csrc/mpcqp_swing_leg.h compiled with g++ and driven tick by tick: the same checks."""
+    worst = _report("mpcqp_swing_leg.h (g++) vs swing.npz", swing_ref.compare_fixture(fx, _header_run(fx, leg)))
     assert worst < CPU_BOUND
+
+
+def _edges_fixture_is_what_the_issue_asks(fxe):
+    """The second fixture's own promises: full non-symmetric gains in two groups, thigh z,
+    commanded z velocity and the three constants off their defaults."""
+    kp, kd = fxe["kp"], fxe["kd"]
+    assert kp.shape == kd.shape == (6, 3, 3)
+    for k in (kp, kd):
+        assert (k[:3] == k[0]).all() and (k[3:] == k[3]).all() and not (k[0] == k[3]).any()
+        for m in (k[0], k[3]):
+            assert len(set(m.reshape(-1).tolist())) == 9 and not np.allclose(m, m.T)
+            off = np.abs(m[~np.eye(3, dtype=bool)])
+            assert off.min() >= 0.1 * np.abs(np.diag(m)).max()
+    th = fxe["thighs"][..., 2]
+    assert (np.abs(th) >= 0.02).all() and (np.abs(th) <= 0.08).all() and len(set(th.reshape(-1).tolist())) == th.size
+    assert (np.abs(fxe["v_body"][:, 2]) >= 0.3).all()
+    assert (float(fxe["dt_control"]), float(fxe["gravity"]), float(fxe["swing_height"])) == (0.002, 3.72, 0.07)
+    assert int(fxe["iterations_between_mpc"]) == 2 and int(fxe["check_every"]) == 2
+    members = [str(m) for m in fxe["member"]]
+    assert "STANDING" in members and "TROTTING10" in members       # one never swings, one has unequal phases
+    golden = os.path.join(ROOT, "tests", "golden")
+    assert os.path.getsize(os.path.join(golden, "swing_edges.npz")) <= os.path.getsize(os.path.join(golden, "swing.npz"))
+
+
+def test_restatement_reproduces_the_edges_run(fxe):
+    """swing_ref against swing_edges.npz -- full gains, thigh z, commanded z velocity, gravity,
+    dt_control and swing_height off their defaults: the same checks as against swing.npz."""
+    _edges_fixture_is_what_the_issue_asks(fxe)
+    worst = _report("swing_ref vs swing_edges.npz", swing_ref.compare_fixture(fxe, _restatement_run(fxe)))
+    assert worst < CPU_BOUND
+
+
+def test_host_compiled_header_reproduces_the_edges_run(fxe, leg):
+    """csrc/mpcqp_swing_leg.h compiled with g++ against swing_edges.npz."""
+    worst = _report("mpcqp_swing_leg.h (g++) vs swing_edges.npz",
+                    swing_ref.compare_fixture(fxe, _header_run(fxe, leg)))
+    assert worst < CPU_BOUND
+
+
+def test_edge_inputs_move_every_robots_torques():
+    """What tests/test_gpu_swing_edges.py compares with swing_ref can fail: on its exact
+    inputs and tick sequences (swing_ref.edge_case at B = 1, 63, 64, 65, and the single calls
+    of swing_ref.edge_one_tick), transposing Kp or
+    Kd, putting any of the five constants back to its default, or zeroing the thighs' z or
+    the commanded z velocity moves swing_ref's tau of EVERY robot by at least 100 x the
+    device bound, norm-wise.  On the second fixture's inputs the same holds for every robot
+    that swings at all (STANDING does not)."""
+    bound = 100 * 4.61e-7
+    defaults = dict(dt_control=0.001, gravity=9.81, swing_height=0.1, touchdown_z=-0.0255, vel_gain=0.03)
+
+    def changes(inp, kw):
+        yield "Kp^T", inp, dict(kw, kp=np.swapaxes(np.asarray(kw["kp"]), -1, -2))
+        yield "Kd^T", inp, dict(kw, kd=np.swapaxes(np.asarray(kw["kd"]), -1, -2))
+        for k, v in defaults.items():
+            assert kw[k] != v
+            yield k, inp, dict(kw, **{k: v})
+        for name, key in (("thigh z", "thighs"), ("v_body z", "v_body")):
+            a = inp[key].copy()
+            a[..., 2] = 0
+            yield name, dict(inp, **{key: a}), kw
+
+    def check(tag, inp, gait, ticks, ibm, kw, robots, mem0=None):
+        base = swing_ref.run_ref(inp, gait, ticks, ibm, mem0=mem0, **kw)
+        for name, inp2, kw2 in changes(inp, kw):
+            o = swing_ref.run_ref(inp2, gait, ticks, ibm, mem0=mem0, **kw2)
+            moved = np.array([swing_ref.norm_err(o["tau"][:, b], base["tau"][:, b]) for b in robots])
+            print(f"{tag} {name}: min over robots {moved.min():.2e}")
+            assert (moved >= bound).all(), (tag, name, moved.min())
+
+    for B in (1, 63, 64, 65):
+        inp, gait, ticks = swing_ref.edge_case(B)
+        kw = dict(swing_ref.EDGE_CONSTS, kp=swing_ref.EDGE_KP, kd=swing_ref.EDGE_KD)
+        check(f"B={B}", inp, gait, ticks, swing_ref.EDGE_IBM, kw, range(B))
+    for B, seed in ((5, 440), (5, 441), (5, 442), (5, 443), (65, 430)):      # the single calls from a swing under way
+        inp, gait, ticks, mem0 = swing_ref.edge_one_tick(B, 5, seed)
+        check(f"one call, B={B} seed {seed}", inp, gait, ticks, swing_ref.EDGE_IBM, kw, range(B), mem0=mem0)
+    fxe = swing_ref.load_fixture("swing_edges.npz")
+    B, T = fxe["tau"].shape[:2]
+    kw = dict(dt_control=float(fxe["dt_control"]), gravity=float(fxe["gravity"]), swing_height=float(fxe["swing_height"]),
+              touchdown_z=0.031, vel_gain=0.11, kp=fxe["kp"], kd=fxe["kd"])
+    swings = [b for b in range(B) if (np.nan_to_num(fxe["swing_state"][b]) > 0).any()]
+    assert len(swings) == B - 1
+    check("swing_edges.npz", swing_ref.fixture_inputs(fxe), fxe["gait"], np.tile(np.arange(T)[:, None], (1, B)),
+          int(fxe["iterations_between_mpc"]), kw, swings)
 
 
 def _curve(leg, T, cur, init, fin, h):
@@ -228,6 +333,38 @@ def test_decisions_of_header_and_restatement_agree(leg):
                     assert (st != 0) == bool(sw[0, l]) and (st == 2) == bool(fin[0, l]), (rec, ibm, tick, l)
                     assert sv.value == val[0, l]
                     assert (sv.value > 0) == (st != 0) and (not fin[0, l] or abs(sv.value - 1.0) < 1e-6)
+    # the integer edges (swing_ref.decision_edges: ticks at +-2^31, -1, 0 and around the span;
+    # period 1, duration 0, a stance that fills the period on one leg, wrapping and negative
+    # offsets, malformed periods; span up to 2^31) against Python's own integers
+    for ibm, rows in swing_ref.decision_edges().items():
+        for tick, rec in rows:
+            for l in range(4):
+                sw, fin, cs, nsw = swing_ref.decide_exact(tick, ibm, rec, l)
+                sv.value = -1.0
+                st = leg.decide(tick, ibm, int(rec[0]), int(rec[1 + l]), int(rec[5 + l]), ctypes.byref(sv))
+                assert st == (2 if fin else 1 if sw else 0), (ibm, tick, rec, l, st, cs, nsw)
+                if not sw:
+                    assert sv.value == 0.0
+                elif ibm * int(rec[0]) <= 2 ** 20:
+                    # the float32 phase is the only inexact step: half an ulp, <= 2^-25, divided by the
+                    # swing fraction; doubled
+                    tol = 2.0 ** -24 / (1.0 - int(rec[5 + l]) / int(rec[0]))
+                    assert abs(sv.value - cs / nsw) <= tol, (ibm, tick, rec, l, sv.value, cs / nsw)
+                else:
+                    assert np.isfinite(sv.value) and sv.value > 0
+                if rec[0] > 0:       # the restatement says the same, value included
+                    rsw, rfin, rval = swing_ref.swing_state(np.array([tick]), ibm, rec[None])
+                    assert (bool(rsw[0, l]), bool(rfin[0, l]), rval[0, l]) == (sw, fin, sv.value)
+    # some of them by hand: TROTTING10 at 20 iterations per MPC step, span 200
+    trot = (10, (0, 5, 5, 0), (5, 5, 5, 5))
+    rec = np.array([trot[0], *trot[1], *trot[2]])
+    assert swing_ref.decide_exact(-1, 20, rec, 0) == (True, False, 99, 100)        # c = 199
+    assert swing_ref.decide_exact(-1, 20, rec, 1)[0] is False                      # cs = 199
+    assert swing_ref.decide_exact(-2 ** 31, 20, rec, 0) == (True, False, 52, 100)         # -2^31 mod 200 = 152
+    assert swing_ref.decide_exact(-2 ** 31, 20, rec, 1) == (False, False, 152, 100)
+    assert swing_ref.decide_exact(2 ** 31 - 1, 20, rec, 1) == (True, False, 47, 100)       # 2^31 - 1 mod 200 = 47
+    assert swing_ref.decide_exact(2 ** 31 - 1, 20, rec, 0) == (False, False, 147, 100)
+    assert swing_ref.decide_exact(100, 20, rec, 1) == (True, True, 100, 100)               # the finishing tick
 
 
 def test_standing_never_swings_and_never_touches_swing_mem(leg):
