@@ -377,14 +377,21 @@ int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, c
  *   est_state    [B][MPCQP_EST_STRIDE] float64 in/out, 16-byte aligned: x[18], initialised
  *                        (0 / 1), 5 x 0, P[18][18] row-major (symmetric) at 24, 4 x 0.  An
  *                        all-zero record is "not initialised": x = 0, P = p0 I.  A caller may
- *                        seed x, P and initialised = 1 itself.
+ *                        seed x, P and initialised = 1 itself.  Any non-zero initialised word
+ *                        (a NaN included) marks the record initialised; a tick rewrites it to
+ *                        1.  The padding words are neither read nor written.
  * Outputs, each nullable:
  *   root_states  [B][13]  pos = p_b, quat (x, y, z, w) copied from the input, lin_vel = v_b,
  *                        ang_vel = R_q w_b (world frame)
  *   feet_world   [B][4][3]  p_1 .. p_4
  *   status       [B]     MPCQP_STATUS_OK, or MPCQP_STATUS_NONFINITE for a robot with a
- *                        non-finite input: its record is not written and its outputs are
- *                        formed from the record as it was; no other robot is affected
+ *                        non-finite input (quat, gyro, accel, q, qdot, trust, geom[0..4]) or
+ *                        an initialised record whose x, P or initialised word is not
+ *                        finite: its record is not written and its outputs are formed from
+ *                        the record as it was (so a non-finite x is handed on, under this
+ *                        status, until the caller reseeds the record); no other robot is
+ *                        affected.  A record that is not initialised is not read beyond
+ *                        that word
  * The tick, with (p_i, J_i) the foot and its Jacobian in the base frame, t_i the clipped
  * trust, k_i = 1 + (1 - t_i) suspicion and x^-, P^- the record:
  *   r_i = R_q p_i,  rd_i = R_q (w_b x p_i + J_i qdot_i),  a = R_q a_b - (0, 0, g)
@@ -440,7 +447,14 @@ int mpcqp_set_estimator(mpcqp_ctx* ctx, double dt, double gravity, double sigma_
  *   touch        [B][4]  the touch sensor per foot (FL, FR, RL, RR); nullable
  *   att_state    [B][MPCQP_ATT_STRIDE] float64 in/out, 16-byte aligned: q (w, x, y, z),
  *                        initialised (0 / 1), gyro bias b[3].  An all-zero record is "not
- *                        initialised".  A caller may seed q, b and initialised = 1 itself.
+ *                        initialised".  A caller may seed q, b and initialised = 1 itself; q
+ *                        is normalised by the tick, so any length from 1e-140 to 1e140 will do
+ *                        (below, the squares the normalisation sums are subnormal: at 1e-160
+ *                        the result is unit to 5e-4 only).
+ *                        A seeded q of length 0, or one so long that the tick's products of
+ *                        its entries overflow (1e150, say), is misuse: that tick writes a NaN q under
+ *                        MPCQP_STATUS_OK, and from the next tick on the robot is refused
+ *                        (MPCQP_STATUS_NONFINITE, record unchanged) until it is reseeded
  * Outputs, each nullable (a NULL output is not written):
  *   quat         [B][4]  (w, x, y, z), unit length; its sign is not canonicalised
  *   gyro_out     [B][3]  w_b - b, the input bitwise while b = 0

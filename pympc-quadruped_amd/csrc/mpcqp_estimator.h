@@ -12,6 +12,9 @@
 // of two columns of P, and P -= h h^T / s is a rank-1 update.  No 28 x 28 factorisation.
 // The leg algebra is mpcqp_kin_leg.h; all arithmetic is float64 with FP contraction off,
 // and each float32 output is rounded once, at its store.
+#include <math.h>
+#include <string.h>
+
 #include "mpcqp_kin_leg.h"
 
 constexpr int EST_NX = 18, EST_INIT = 18, EST_P = 24, EST_STRIDE = 352;
@@ -43,6 +46,8 @@ struct EstShared {
   EstLeg leg[4];
   double acc[3], wworld[3];              // R_q a_b - g e_z, R_q w_b
   int bad[4];                            // a non-finite input seen by leg lane l
+  // lane j saw a non-finite x_j, P column j or `initialised` word: a byte per lane, read back as three words
+  unsigned char __attribute__((aligned(16))) rec_bad[24];
 };
 
 __device__ inline bool est_finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
@@ -64,21 +69,19 @@ __global__ __launch_bounds__(kEstThreads) void mpcqp_estimate_kernel(
   double* rec = est_state + (size_t)EST_STRIDE * (live ? b : 0);
 
   // ---- the record: x_j, column j of P; an all-zero record starts from (0, P0 I)
-  double x = 0.0, Pc[EST_NX];
+  // (a NaN `initialised` word is non-zero: the record counts as initialised, and is refused).
+  double x = 0.0, Pc[EST_NX], iw = 0.0;
 #pragma unroll
   for (int i = 0; i < EST_NX; ++i) Pc[i] = 0.0;
+  // Every load of the record is issued here, before the `initialised` word is looked at,
+  // and none of them is used until the leg algebra below is done: the record and the sensors
+  // are in flight together, one memory latency and not three in a row.
   if (live) {
-    const bool init = rec[EST_INIT] != 0.0;
-    if (init) {
-      x = rec[j];
+    iw = rec[EST_INIT];
+    x = rec[j];
 #pragma unroll
-      for (int i = 0; i < EST_NX; ++i) Pc[i] = rec[EST_P + EST_NX * i + j];
-    } else {
-#pragma unroll
-      for (int i = 0; i < EST_NX; ++i) Pc[i] = i == j ? ep.p0 : 0.0;
-    }
+    for (int i = 0; i < EST_NX; ++i) Pc[i] = rec[EST_P + EST_NX * i + j];
   }
-  const double x_minus = x;
 
   // ---- the sensors: lane l < 4 of a robot does leg l (step 1)
   double qw = 0.0, qx = 0.0, qy = 0.0, qz = 0.0;
@@ -86,6 +89,17 @@ __global__ __launch_bounds__(kEstThreads) void mpcqp_estimate_kernel(
     const int leg = j;
     const size_t bl = (size_t)b * 4 + leg;
     double ql[3], qd[3], w[3], ab[3], g[5];
+    qw = (double)quat[4 * (size_t)b], qx = (double)quat[4 * (size_t)b + 1], qy = (double)quat[4 * (size_t)b + 2],
+    qz = (double)quat[4 * (size_t)b + 3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      w[k] = (double)gyro[3 * (size_t)b + k];
+      ab[k] = (double)accel[3 * (size_t)b + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) g[k] = geom[KIN_STRIDE * (size_t)b + k];
+    const float tr = trust[bl];
+    // (the joints last: their layout is a branch, and a load behind it would wait for them)
     if (ep.dof_layout) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -99,16 +113,6 @@ __global__ __launch_bounds__(kEstThreads) void mpcqp_estimate_kernel(
         qd[k] = (double)qdot[bl * 3 + k];
       }
     }
-    qw = (double)quat[4 * (size_t)b], qx = (double)quat[4 * (size_t)b + 1], qy = (double)quat[4 * (size_t)b + 2],
-    qz = (double)quat[4 * (size_t)b + 3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      w[k] = (double)gyro[3 * (size_t)b + k];
-      ab[k] = (double)accel[3 * (size_t)b + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) g[k] = geom[KIN_STRIDE * (size_t)b + k];
-    const float tr = trust[bl];
     bool ok = isfinite(qw) && isfinite(qx) && isfinite(qy) && isfinite(qz) && est_finite3(w) && est_finite3(ab) &&
               est_finite3(ql) && est_finite3(qd) && isfinite(tr);
 #pragma unroll
@@ -134,12 +138,22 @@ __global__ __launch_bounds__(kEstThreads) void mpcqp_estimate_kernel(
       swing_mat3(Rq, w, sh.wworld);
     }
   }
+  // a fresh record: whatever it holds beyond its `initialised` word is discarded
+  if (live && !(iw != 0.0)) {
+    x = 0.0;
+#pragma unroll
+    for (int i = 0; i < EST_NX; ++i) Pc[i] = i == j ? ep.p0 : 0.0;
+  }
+  const double x_minus = x;
+  // An initialised record that holds a non-finite x, P or `initialised` word is refused like
+  // a non-finite input.  Each lane judges what it holds and the verdicts meet in LDS; they
+  // are read in the store phase, many barriers on.  (A fresh record's 0 and p0 I pass.)
+  // The verdict itself is formed below, among the prediction's LDS reads.
   sh.xm[j] = x;
 #pragma unroll
   for (int i = 0; i < EST_NX; ++i) sh.P[EST_NX * i + j] = Pc[i];
   __syncthreads();
 
-  const bool bad = (sh.bad[0] | sh.bad[1] | sh.bad[2] | sh.bad[3]) != 0;
   const double dt = ep.dt;
 
   // ---- the prediction (step 4): x = A x^- + B a, P = A P A^T + Q with A = I + dt E_pv.
@@ -152,13 +166,30 @@ __global__ __launch_bounds__(kEstThreads) void mpcqp_estimate_kernel(
   }
   {
     const double qj = dt * (j < 3 ? ep.sigma_p : j < 6 ? ep.sigma_v : ep.sigma_f * sh.leg[j >= 6 ? (j - 6) / 3 : 0].k);
+    // the record's verdict (see above), here so that it runs while the reads below are on
+    // their way.  0 * v is 0 for a finite v and NaN for any other, and a NaN survives the
+    // sums: twenty multiply-adds on two chains, nothing compared until the end.
+    double z0 = 0.0 * iw, z1 = 0.0 * x_minus;
+#pragma unroll
+    for (int i = 0; i < EST_NX; i += 2) {
+      z0 = fma(0.0, Pc[i], z0);
+      z1 = fma(0.0, Pc[i + 1], z1);
+    }
+    sh.rec_bad[j] = (z0 + z1) == 0.0 ? 0 : 1;
     double Pn[EST_NX];
 #pragma unroll
     for (int i = 0; i < EST_NX; ++i) {
       const double pa = i < 3 ? Pc[i + 3] : 0.0;
-      const double pb = j < 3 ? sh.P[EST_NX * i + j + 3] : 0.0;
+      // (every lane reads, from a column that exists, and lanes 3 .. 17 discard: a read
+      // under a branch would wait for its own latency, eighteen times in a row)
+      const int jc = j < 3 ? j + 3 : j;
+      const double pbv = sh.P[EST_NX * i + jc];
+      const double pb = j < 3 ? pbv : 0.0;
       double v = Pc[i] + dt * (pa + pb);
-      if (i < 3) v = v + (dt * dt) * (j < 3 ? sh.P[EST_NX * (i + 3) + j + 3] : 0.0);
+      if (i < 3) {
+        const double pcv = sh.P[EST_NX * (i + 3) + jc];
+        v = v + (dt * dt) * (j < 3 ? pcv : 0.0);
+      }
       Pn[i] = i == j ? v + qj : v;
     }
 #pragma unroll
@@ -214,8 +245,11 @@ __global__ __launch_bounds__(kEstThreads) void mpcqp_estimate_kernel(
   for (int i = 0; i < EST_NX; ++i) Pc[i] = 0.5 * (Pc[i] + sh.P[EST_NX * j + i]);
 
   if (!live) return;
-  // ---- stores: a robot with a non-finite input keeps its record, and its outputs are
-  // formed from the state as it was (step 7)
+  unsigned long long rb[3];
+  memcpy(rb, sh.rec_bad, sizeof rb);   // bytes 18 .. 23 belong to nobody
+  const bool bad = (sh.bad[0] | sh.bad[1] | sh.bad[2] | sh.bad[3]) != 0 || (rb[0] | rb[1] | (rb[2] & 0xffffull)) != 0;
+  // ---- stores: a robot with a non-finite input or record keeps its record, and its
+  // outputs are formed from the state as it was (step 7)
   if (!bad) {
     rec[j] = x;
 #pragma unroll

@@ -265,3 +265,49 @@ def make_trajectory(B, T, seed):
         q = quat_mul(q, quat_exp(rate[i] * dt))
         q = q / np.linalg.norm(q, axis=1, keepdims=True)
     return traj
+
+
+# ---- edge inputs shared by tests/test_att.py (the header on the host) and
+# tests/test_gpu_att_edges.py (the device)
+TRUST_WINDOWS = (0.2, 0.0, 0.5, 1e-300)
+G32 = np.float32(9.81)
+# first tick: n = 0; straight down; still under the m_z < -1 + 1e-12 threshold in float64; just
+# above it, where the shortest arc is nearly singular (twice); a subnormal; tiny; huge; sideways
+FIRST_ACCEL = np.float32([[0, 0, 0], [0, 0, -9.81], [0, 1e-5, -9.81], [1e-3, 0, -9.81], [1e-2, 1e-2, -9.81],
+                          [0, 0, 1e-44], [1e-30, 0, 0], [3e38, 0, 0], [9.81, 0, 0]])
+# the gate: |a| = g, 2 g (float32(19.62) is just past it), beyond (gamma = 0: rows 2, 3), tiny, huge
+GATE_ACCEL = np.float32([[0, 0, 9.81], [0, 0, 19.62], [0, 0, 19.63], [0, 0, 25], [1e-30, 0, 0], [3e38, 0, 0]])
+GATE_CLOSED = (2, 3)
+GATE_CONSTANTS = dict(kappa_ref=2.0)
+TILT = np.array([0.96, 0.18, -0.2, 0.07]) / np.linalg.norm([0.96, 0.18, -0.2, 0.07])
+# either side of |theta| = 1e-8 at dt = 1e-3, and 0
+SWITCH_GYRO = np.float32([[0.9e-5, 0, 0], [1.1e-5, 0, 0], [0, 0, 0]])
+LARGE_RATES = np.float32([1e3, 5e3, 2e4])       # |theta| up to 23 rad per tick at dt = 1e-3
+HUGE_RATES = np.float32([1e6, 3e38])
+SEED_NORMS = (2.0, 1e-3, 1e-160)
+MISUSE_NORMS = (0.0, 1e150)
+
+
+def rate_rows(w):
+    w = np.asarray(w, np.float32)
+    return np.stack([w, -w / np.float32(2), w / np.float32(4)], 1).astype(np.float32)
+
+
+def trust_edges(ibm):
+    """The leg controller's decision table (swing_ref.decision_edges) for one
+    iterations_between_mpc, a robot per row: (tick [B] int32, gait [B,9] int32)."""
+    import swing_ref
+    rows = swing_ref.decision_edges()[ibm]
+    return np.array([t for t, _ in rows], np.int32), np.stack([r for _, r in rows]).astype(np.int32)
+
+
+def level(B):
+    """gyro 0, accel (0, 0, g) for B robots."""
+    return dict(gyro=np.zeros((B, 3), np.float32), accel=np.tile(np.float32([0, 0, 9.81]), (B, 1)))
+
+
+def touch_at_threshold(threshold=0.25):
+    """[3,4] float32: the threshold exactly, one float32 below, one above (the threshold is a
+    float32 value, so the comparison in float64 is exact)."""
+    t = np.float32(threshold)
+    return np.stack([np.full(4, v, np.float32) for v in (t, np.nextafter(t, np.float32(-1)), np.nextafter(t, np.float32(1)))])

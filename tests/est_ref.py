@@ -24,6 +24,10 @@ INPUTS = ("quat", "gyro", "accel", "q", "qdot", "trust", "geom")
 # per robot, largest over ticks and robots, as tests/test_est.py measures and prints it: the
 # problem's rounding sensitivity d, from which tests/test_gpu_est.py takes its bounds
 D_X, D_P = 1.94e-11, 4.8e-15
+# the same figure for the long regimes of regime_trajectory(7, 200) below, where the generator's
+# d does not hold (tests/test_est.py measures and prints them): regime -> (d_x, d_P)
+D_REGIME = {"swing": (7.17e-12, 1.95e-14), "stance": (5.86e-11, 1.96e-15), "noiseless": (8.56e-10, 1.96e-15)}
+REGIME_SEED = 11
 
 
 def measurement_matrix():
@@ -73,6 +77,10 @@ def estimate_step(state, inputs, constants=None, form="batch"):
     f64 = lambda k: np.asarray(inputs[k]).astype(np.float64)
     quat, w, ab, q, qd, tr, geom = (f64(k) for k in INPUTS)
     bad = ~np.all([np.isfinite(a.reshape(B, -1)).all(1) for a in (quat, w, ab, q, qd, tr, geom[:, :5])], axis=0)
+    # an initialised record (any non-zero word, NaN included) with a non-finite x, P or
+    # `initialised` word is refused like a non-finite input; a fresh record is not read
+    used = np.concatenate([state[:, :NX + 1], state[:, P_OFF:P_OFF + NX * NX]], axis=1)
+    bad |= (state[:, INIT] != 0.0) & ~np.isfinite(used).all(1)
     with np.errstate(all="ignore"):
         Rq = kin_ref.quat2matrix_eigen(quat)
         p, _, Jb = kin_ref.chain(geom, q)
@@ -190,6 +198,105 @@ def make_trajectory(B, T, seed):
     trust = np.where((kind == 3)[..., None], out, trust)                # outside [0, 1]: clipped by the filter
     return [dict(quat=quat[i].astype(f), gyro=gyro[i].astype(f), accel=accel[i].astype(f), q=q[i].astype(f),
                  qdot=qdot[i].astype(f), trust=trust[i].astype(f), geom=geom) for i in range(T)]
+
+
+# ---- edge inputs shared by tests/test_est.py (the kernel on host threads) and
+# tests/test_gpu_est_edges.py (the device)
+NONFINITE = (np.nan, np.inf, -np.inf)
+WIDTH = dict(quat=4, gyro=3, accel=3, q=12, qdot=12, trust=4, geom=5)
+DIRTY = (1, 5, 6)          # of B = 7: a middle slot, the second workgroup's last slot, the tail
+TRUST_OUTSIDE = np.float32([-0.0, 1.0 + 2.0 ** -23, 3e38, -3e38])      # behaves as ...
+TRUST_CLIPPED = np.float32([0.0, 1.0, 1.0, 0.0])
+TRUST_INSIDE = np.float32([1e-45, 1.0 - 2.0 ** -24, 0.5, 0.25])        # a subnormal, one ulp under 1
+# words of the record for a non-finite value: x_0, x_4, x_17, P[0][0], P[4][4], P[17][17],
+# P[2][11], P[11][2], P[17][0], and the `initialised` word
+RECORD_WORDS = (0, 4, 17, P_OFF, P_OFF + 4 * NX + 4, P_OFF + 17 * NX + 17, P_OFF + 2 * NX + 11, P_OFF + 11 * NX + 2,
+                P_OFF + 17 * NX, INIT)
+PADDING = tuple(range(19, 24)) + tuple(range(348, 352))
+
+
+def nonfinite_cases():
+    """One launch per (input, element) of a robot: [(key, element, value, dirty robot)], the
+    value alternating NaN / +inf / -inf and the robot rotating through DIRTY.  43 cases."""
+    cases = [(k, e) for k in INPUTS for e in range(WIDTH[k])]
+    return [(k, e, NONFINITE[i % 3], DIRTY[i % 3]) for i, (k, e) in enumerate(cases)]
+
+
+def dof_cases():
+    """The same in the dof-state layout: a position and a velocity slot of each leg, as
+    (key, element, value, dirty robot) on the split arrays.  8 cases."""
+    cases = [(("q", "qdot")[s], 3 * leg + (leg + s) % 3) for leg in range(4) for s in range(2)]
+    return [(k, e, NONFINITE[i % 3], DIRTY[i % 3]) for i, (k, e) in enumerate(cases)]
+
+
+def poisoned(inp, key, element, value, robot):
+    out = {k: v.copy() for k, v in inp.items()}
+    out[key][robot, element] = value
+    return out
+
+
+def record_cases():
+    """A non-finite word in an initialised record: [(word, value, dirty robot)], robots 2 (a
+    workgroup's last slot) and 6 (the tail) of B = 7."""
+    return [(w, np.nan if w == INIT else NONFINITE[i % 3], (2, 6)[i % 2]) for i, w in enumerate(RECORD_WORDS)]
+
+
+def quat_variants(quat):
+    """quat [B,4] float32 -> the same attitude given as 2 q, q / 2, 0 and -q."""
+    quat = np.asarray(quat, np.float32)
+    return dict(double=quat * np.float32(2), half=quat * np.float32(0.5), zero=np.zeros_like(quat), negated=-quat)
+
+
+def regime_trajectory(B, T, regime):
+    """The generator's trajectory held in one regime for T ticks: `swing` (every trust 0),
+    `stance` (every trust 1) or `noiseless` (the generator's trust, sigma_p = sigma_v = sigma_f =
+    suspicion = 0).  Returns (trajectory, constants)."""
+    traj = make_trajectory(B, T, seed=REGIME_SEED)
+    if regime == "noiseless":
+        return traj, dict(sigma_p=0.0, sigma_v=0.0, sigma_f=0.0, suspicion=0.0)
+    value = np.float32({"swing": 0.0, "stance": 1.0}[regime])
+    return [dict(t, trust=np.full_like(t["trust"], value)) for t in traj], None
+
+
+def same_bits(a, b):
+    """Bitwise equality: NaN payloads and the sign of zero count."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def assert_refused(start, quat, clean, dirty, robot, skip=(), tag=None):
+    """What a refusal is.  `clean` and `dirty` are (records, outputs) of the same launch from
+    the records `start` without and with the non-finite value, sentinel rows included; `quat`
+    is the dirty launch's.  The dirty robot: status 4, its record bitwise as it was, position,
+    velocity and feet the float32 of the old x, the orientation the input quaternion's bits;
+    every other row, sentinels included, bitwise the clean launch's."""
+    (sc, oc), (sd, od) = clean, dirty
+    f = np.float32
+    assert same_bits(sd[robot], start[robot]), tag
+    if "status" not in skip:
+        assert od["status"][robot] == STATUS_NONFINITE, (tag, od["status"])
+        assert oc["status"][robot] == 0, tag
+    if "root_states" not in skip:
+        root = od["root_states"][robot]
+        assert same_bits(root[0:3], start[robot, 0:3].astype(f)) and same_bits(root[7:10], start[robot, 3:6].astype(f)), tag
+        assert same_bits(root[3:7], np.asarray(quat, f)[robot, [1, 2, 3, 0]]), tag
+    if "feet_world" not in skip:
+        assert same_bits(od["feet_world"][robot].ravel(), start[robot, 6:18].astype(f)), tag
+    others = [b for b in range(sd.shape[0]) if b != robot]
+    assert same_bits(sd[others], sc[others]), tag
+    for k in oc:
+        assert same_bits(od[k][others], oc[k][others]), (tag, k)
+
+
+def worst_err(states, ref):
+    """Largest norm-wise distance per robot over the ticks of two [T+1,B,STRIDE] runs: (x, P)."""
+    dx = dP = 0.0
+    for i in range(1, len(ref)):
+        xa, Pa, _ = unpack(states[i])
+        xr, Pr, _ = unpack(ref[i])
+        for b in range(xa.shape[0]):
+            dx, dP = max(dx, norm_err(xa[b], xr[b])), max(dP, norm_err(Pa[b], Pr[b]))
+    return dx, dP
 
 
 def run(traj, constants=None, form="batch", state=None):

@@ -142,3 +142,49 @@ def urdf_text(geom=(0.2, 0.05, 0.08, 0.21, 0.22), axis=None, rpy=None, offset=No
 def load_fixture():
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kin.npz")
     return {k: v for k, v in np.load(path).items()}
+
+
+# ---- edge inputs shared by tests/test_kin.py (the header on the host) and
+# tests/test_gpu_kin_edges.py (the device)
+A1, ALIENGO = (0.183, 0.047, 0.08505, 0.2, 0.2), (0.2399, 0.051, 0.083, 0.25, 0.25)
+EDGE_ROWS = ("q = 0", "q = (pi, -pi, pi)", "calf = 0", "q = (1e4, -1e4, 3e3)", "q = (pi/2, pi/2, -pi)", "quat = 0",
+             "2 quat", "quat / 2", "-quat", "geom = 0", "pos = (1e6, -1e6, 1e3)", "large vel, omega, qdot")
+
+
+def ordinary(B, seed):
+    """B seeded robots away from every edge: (geom [B,5], inputs dict, rot [B,3,3] float32 --
+    another orientation's matrix, for the layout that takes R_base from the caller)."""
+    rng = np.random.default_rng(seed)
+    f = np.float32
+    unit = lambda a: a / np.linalg.norm(a, axis=1, keepdims=True)
+    geom = np.array([A1, ALIENGO])[np.arange(B) % 2]
+    inp = dict(quat=unit(rng.standard_normal((B, 4))).astype(f), pos=rng.uniform(-1, 1, (B, 3)).astype(f),
+               vel=rng.uniform(-2, 2, (B, 3)).astype(f), omega=rng.uniform(-2, 2, (B, 3)).astype(f),
+               q=(np.tile([0.0, 0.8, -1.6], 4) + rng.uniform(-0.5, 0.5, (B, 12))).astype(f),
+               qdot=rng.uniform(-3, 3, (B, 12)).astype(f))
+    rot = quat2matrix_eigen(unit(rng.standard_normal((B, 4)))).astype(f)
+    return geom, inp, rot
+
+
+def edge_poses():
+    """The EDGE_ROWS, one robot each, everything else ordinary: (geom, inputs, rot)."""
+    geom, inp, rot = ordinary(len(EDGE_ROWS), seed=17)
+    f, pi = np.float32, np.pi
+    inp["q"][0] = 0.0
+    inp["q"][1] = np.tile(f([pi, -pi, pi]), 4)
+    inp["q"][2, 2::3] = 0.0
+    inp["q"][3] = np.tile(f([1e4, -1e4, 3e3]), 4)
+    inp["q"][4] = np.tile(f([pi / 2, pi / 2, -pi]), 4)
+    inp["quat"][5] = 0.0
+    inp["quat"][6] *= f(2)
+    inp["quat"][7] *= f(0.5)
+    inp["quat"][8] *= f(-1)
+    geom[9] = 0.0
+    inp["pos"][10] = f([1e6, -1e6, 1e3])
+    inp["vel"][11], inp["omega"][11], inp["qdot"][11] = f([1e3, -1e3, 50]), f([200, -300, 100]), f(1e3)
+    return geom, inp, rot
+
+
+# a NaN in: (input, index within the robot's row); `q` at a thigh, a calf and a hip joint
+NAN_CASES = (("quat", 2), ("pos", 1), ("vel", 0), ("omega", 2), ("q", 4), ("q", 11), ("q", 6), ("qdot", 1),
+             ("geom", 0), ("geom", 1), ("geom", 2), ("geom", 3), ("geom", 4), ("rot", 5))

@@ -26,6 +26,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import att_edge_checks
 import att_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -398,3 +399,73 @@ def test_non_finite_input_leaves_that_robot_alone(robot, key, value):
                 assert (got["trust"][1] == 0).all()
             else:
                 assert np.array_equal(np.float32(got["trust"][1]), np.float32(ref_out["trust"][1]))
+
+
+# ---- the CPU twins of tests/test_gpu_att_edges.py: the checks of tests/att_edge_checks.py
+# on the host build of the header, so that each assertion made on the device is shown to hold
+# for correct code without one
+
+@pytest.fixture(scope="module")
+def edge_launch(robot):
+    def launch(state, inp, constants):
+        st = np.vstack([state, np.full((2, att_ref.STRIDE), float(SENTINEL))])
+        out = host_launch(robot, st, att_ref.select(inp, ("tick", "gait", "ibm", "touch")), constants)
+        assert (st[-2:] == SENTINEL).all() and all((v[-2:] == SENTINEL).all() for v in out.values())
+        return st, out
+    return launch
+
+
+@pytest.mark.parametrize("ibm", [1, 20, 2 ** 20])
+def test_edge_trust_on_the_decision_table(edge_launch, ibm):
+    """3a.  B = 42, 42, 43 rows; windows 0.2, 0, 0.5, 1e-300."""
+    assert len(att_ref.trust_edges(ibm)[0]) == (43 if ibm == 2 ** 20 else 42)
+    for window in att_ref.TRUST_WINDOWS:
+        att_edge_checks.check_trust_table(edge_launch, ibm, window)
+
+
+def test_edge_trust_exact_restatement_catches_a_float32_ramp():
+    """The exact check matters: phi formed in float32 at nst = 2^30 would be out by 2^-24
+    relative at least somewhere on the table -- k - 1/2 does not fit a float32 there."""
+    tick, gait = att_ref.trust_edges(2 ** 20)
+    worst = 0.0
+    for b in range(len(tick)):
+        for leg in range(4):
+            swing, _, cs, nsw = att_edge_checks.swing_ref.decide_exact(tick[b], 2 ** 20, gait[b], leg)
+            nst = int(gait[b, 5 + leg]) * 2 ** 20
+            exact = att_edge_checks.trust_exact(tick[b], 2 ** 20, gait[b], leg, 0.2)
+            if swing or exact in (0, 1):
+                continue
+            k = nst if cs == 0 else cs - nsw
+            phi = np.float32(np.float32(k) - np.float32(0.5)) / np.float32(nst)
+            got = min(np.float32(1), phi / np.float32(0.2), (np.float32(1) - phi) / np.float32(0.2))
+            worst = max(worst, abs(float(got) - float(exact)) / float(exact))
+    assert worst >= 100 * 2.0 ** -24
+
+
+def test_edge_touch_threshold(edge_launch):
+    att_edge_checks.check_touch_threshold(edge_launch)
+
+
+def test_edge_first_tick(edge_launch):
+    first, later = att_edge_checks.check_first_tick(edge_launch)
+    print(f"\nfirst tick on the host: {first:.2e}, after 5 ticks {later:.2e}")
+
+
+def test_edge_gate_and_switch(edge_launch):
+    gate, switch = att_edge_checks.check_gate_and_switch(edge_launch)
+    print(f"\ngate corners on the host: {gate:.2e}, small-angle switch {switch:.2e}")
+
+
+def test_edge_large_rotation(edge_launch):
+    large, huge = att_edge_checks.check_large_rotation(edge_launch)
+    print(f"\nlarge rotation on the host: {large:.2e}; at 1e6 and 3e38 rad/s (both sides glibc) "
+          + ", ".join(f"{v:.2e}" for v in huge))
+
+
+def test_edge_seeded_records(edge_launch):
+    seeded = att_edge_checks.check_seeded_records(edge_launch)
+    print(f"\nseeded quaternions of norm 2, 1e-3, 1e-160 on the host: {seeded:.2e}")
+
+
+def test_edge_refusal_across_a_workgroup(edge_launch):
+    att_edge_checks.check_refusal_across_a_workgroup(edge_launch)

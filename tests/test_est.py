@@ -313,3 +313,238 @@ def test_host_run_of_the_kernel_nan_and_constants(kernel):
     for b in range(4):
         assert est_ref.norm_err(st[b, :18], ref[b, :18]) <= est_ref.D_X
         assert est_ref.norm_err(st[b, 24:348], ref[b, 24:348]) <= est_ref.D_P
+
+
+# ---- the CPU twins of tests/test_gpu_est_edges.py: est_ref's edge inputs through the
+# kernel on host threads, so that every assertion made on the device is shown to hold for
+# correct code without one.  B = 7: slots 0, 1, 2, a second workgroup, a tail of one.
+EB = 7
+X_BOUND, P_BOUND, F32_BOUND = 10 * est_ref.D_X, 10 * est_ref.D_P, 2.4e-7
+
+
+def host_tick(kernel, start, inp, layout="split", constants=None):
+    """One host launch from the records `start` [B]: (records, outputs), each with two sentinel rows."""
+    st = np.vstack([start, np.full((2, est_ref.STRIDE), -77.0)])
+    out = host_launch(kernel, st, inp, layout, constants)
+    assert (st[-2:] == -77).all() and all((v[-2:] == -77).all() for v in out.values())
+    return st, out
+
+
+@pytest.fixture(scope="module")
+def edge_start():
+    """The generator's trajectory for EB robots (Aliengo / A1 alternating), the records after
+    5 ticks and the inputs of the sixth."""
+    traj = est_ref.make_trajectory(EB, 12, seed=7)
+    return traj, est_ref.run(traj[:5])[0][-1]
+
+
+def test_edge_case_tables():
+    cases = est_ref.nonfinite_cases()
+    assert len(cases) == 43 and len(est_ref.dof_cases()) == 8
+    assert {(k, e) for k, e, _, _ in cases} == {(k, e) for k in est_ref.INPUTS for e in range(est_ref.WIDTH[k])}
+    assert {r for *_, r in cases} == {1, 5, 6} and {repr(v) for _, _, v, _ in cases} == {"nan", "inf", "-inf"}
+    assert {(k, e // 3) for k, e, _, _ in est_ref.dof_cases()} == {(k, leg) for k in ("q", "qdot") for leg in range(4)}
+    assert {r for _, _, r in est_ref.record_cases()} == {2, 6} and len(est_ref.record_cases()) == 10
+
+
+def test_host_kernel_refuses_a_value_one_lane_sees(kernel, edge_start):
+    """2a.  Every (input, element) in turn; the joints, the trust and so the verdict of legs
+    1..3 reach one leg lane only, so a kernel that read sh.bad[0] alone would fail 24 cases."""
+    traj, start = edge_start
+    clean = host_tick(kernel, start, traj[5])
+    for key, e, v, robot in est_ref.nonfinite_cases():
+        inp = est_ref.poisoned(traj[5], key, e, v, robot)
+        est_ref.assert_refused(start, inp["quat"], clean, host_tick(kernel, start, inp), robot, tag=(key, e, v, robot))
+    clean = host_tick(kernel, start, traj[5], "dof")
+    for key, e, v, robot in est_ref.dof_cases():
+        inp = est_ref.poisoned(traj[5], key, e, v, robot)
+        est_ref.assert_refused(start, inp["quat"], clean, host_tick(kernel, start, inp, "dof"), robot, tag=(key, e, v))
+    for word in (5, 6, 7):                                   # nobody reads the geometry record's tail
+        inp = est_ref.poisoned(traj[5], "geom", word, np.nan, 1)
+        sd, od = host_tick(kernel, start, inp, "dof")
+        assert est_ref.same_bits(sd, clean[0]) and all(est_ref.same_bits(od[k], clean[1][k]) for k in od)
+
+
+def test_host_kernel_refusal_on_a_fresh_record(kernel, edge_start):
+    """2b."""
+    traj, _ = edge_start
+    zero = np.zeros((EB, est_ref.STRIDE))
+    clean = host_tick(kernel, zero, traj[0])
+    inp = est_ref.poisoned(traj[0], "q", 7, np.nan, 4)
+    sd, od = host_tick(kernel, zero, inp)
+    est_ref.assert_refused(zero, inp["quat"], clean, (sd, od), 4)
+    assert (sd[4] == 0).all() and (od["root_states"][4, [0, 1, 2, 7, 8, 9]] == 0).all() and (od["feet_world"][4] == 0).all()
+    s2, o2 = host_tick(kernel, sd[:EB], traj[0])
+    assert est_ref.same_bits(s2[4], clean[0][4]) and all(est_ref.same_bits(o2[k][4], clean[1][k][4]) for k in o2)
+
+
+def test_host_kernel_trust_values(kernel, edge_start):
+    """2c.  The clip is on the float32: -0.0, one ulp over 1 and +-3e38 are 0, 1, 1, 0 to the
+    bit.  A subnormal, one ulp under 1 and two fractions follow est_ref; a kernel that read
+    leg 0's trust for every leg would be out by more than 100 bounds."""
+    traj, start = edge_start
+    tile = lambda t: np.tile(t, (EB, 1))
+    a = host_tick(kernel, start, dict(traj[5], trust=tile(est_ref.TRUST_OUTSIDE)))
+    b = host_tick(kernel, start, dict(traj[5], trust=tile(est_ref.TRUST_CLIPPED)))
+    assert est_ref.same_bits(a[0], b[0]) and all(est_ref.same_bits(a[1][k], b[1][k]) for k in a[1])
+    inp = dict(traj[5], trust=tile(est_ref.TRUST_INSIDE))
+    st, out = host_tick(kernel, start, inp)
+    ref, _ = est_ref.estimate_step(start, inp)
+    wrong, _ = est_ref.estimate_step(start, dict(inp, trust=tile(est_ref.TRUST_INSIDE[[0, 0, 0, 0]])))
+    dx, dP = est_ref.worst_err([None, st[:EB]], [None, ref])
+    print(f"\ntrust inside (0, 1) on host threads: x {dx:.2e}, P {dP:.2e}")
+    assert dx <= X_BOUND and dP <= P_BOUND and (out["status"][:EB] == 0).all()
+    assert min(est_ref.worst_err([None, wrong[b:b + 1]], [None, ref[b:b + 1]])[0] for b in range(EB)) >= 100 * X_BOUND
+
+
+def test_host_kernel_refuses_a_nonfinite_record(kernel, edge_start):
+    """2d.  A non-finite x_j, P entry (on and off the diagonal) or `initialised` word of an
+    initialised record: that robot is refused and the others do not notice.  The same words
+    in a record whose `initialised` word is 0 are not read."""
+    traj, start = edge_start
+    clean = host_tick(kernel, start, traj[5])
+    for word, v, robot in est_ref.record_cases():
+        seeded = start.copy()
+        seeded[robot, word] = v
+        dirty = host_tick(kernel, seeded, traj[5])
+        # the clean launch's other robots; the dirty robot is compared with its own seed
+        ref = (np.vstack([clean[0][:robot], seeded[robot:robot + 1], clean[0][robot + 1:]]), clean[1])
+        est_ref.assert_refused(seeded, traj[5]["quat"], ref, dirty, robot, tag=(word, v, robot))
+        again = host_tick(kernel, dirty[0][:EB], traj[6])
+        assert again[1]["status"][robot] == 4 and est_ref.same_bits(again[0][robot], seeded[robot])
+    first = host_tick(kernel, np.zeros((EB, est_ref.STRIDE)), traj[5])
+    fresh = np.zeros((EB, est_ref.STRIDE))
+    fresh[2, [0, 4, 17]] = np.nan
+    fresh[6, [est_ref.P_OFF, est_ref.P_OFF + 29]] = np.nan, np.inf
+    sd, od = host_tick(kernel, fresh, traj[5])
+    assert est_ref.same_bits(sd, first[0]) and all(est_ref.same_bits(od[k], first[1][k]) for k in od)
+    assert (od["status"][:EB] == 0).all()
+
+
+def test_restatement_refuses_a_nonfinite_record(edge_start):
+    traj, start = edge_start
+    clean, oc = est_ref.estimate_step(start, traj[5])
+    for word, v, robot in est_ref.record_cases():
+        seeded = start.copy()
+        seeded[robot, word] = v
+        for form in ("batch", "sequential"):
+            new, out = est_ref.estimate_step(seeded, traj[5], None, form)
+            assert out["status"][robot] == 4 and est_ref.same_bits(new[robot], seeded[robot]), (word, form)
+            keep = [b for b in range(EB) if b != robot]
+            assert (out["status"][keep] == 0).all()
+            if form == "batch":
+                assert est_ref.same_bits(new[keep], clean[keep])
+    fresh = np.zeros((EB, est_ref.STRIDE))
+    fresh[2, 4] = fresh[6, est_ref.P_OFF + 29] = np.nan
+    new, out = est_ref.estimate_step(fresh, traj[5])
+    assert est_ref.same_bits(new, est_ref.estimate_step(np.zeros((EB, est_ref.STRIDE)), traj[5])[0]) and (out["status"] == 0).all()
+
+
+def test_host_kernel_other_words_of_the_record(kernel, edge_start):
+    """2e.  Any non-zero `initialised` word is 1 and is rewritten to 1.0; the padding words
+    keep their bits and change nothing."""
+    traj, start = edge_start
+    clean = host_tick(kernel, start, traj[5])
+    seeded = start.copy()
+    seeded[1, est_ref.INIT], seeded[3, est_ref.INIT] = 2.0, -3.0
+    seeded[:, est_ref.PADDING[:5]], seeded[:, est_ref.PADDING[5:]] = 5.0, 6.0
+    sd, od = host_tick(kernel, seeded, traj[5])
+    pad = list(est_ref.PADDING)
+    assert (sd[:EB, est_ref.INIT] == 1.0).all() and est_ref.same_bits(sd[:EB, pad], seeded[:, pad])
+    sd[:EB, pad] = 0.0
+    assert est_ref.same_bits(sd, clean[0]) and all(est_ref.same_bits(od[k], clean[1][k]) for k in od)
+
+
+def test_host_kernel_quaternion_as_given(kernel, edge_start):
+    """2f.  R_q is the documented polynomial in q, used as given: 2 q, q / 2 and 0 follow
+    est_ref fed the same quaternion (a kernel that normalised q would be out by more than
+    100 bounds for 2 q), 0 gives R = I, and -q gives q's record to the bit."""
+    traj, start = edge_start
+    runs = {}
+    for name in ("given", "double", "half", "zero", "negated"):
+        tr = [dict(t, quat=t["quat"] if name == "given" else est_ref.quat_variants(t["quat"])[name]) for t in traj[:10]]
+        st = start
+        states = [st]
+        for inp in tr:
+            full, out = host_tick(kernel, st, inp)
+            st = full[:EB]
+            states.append(st)
+            assert (out["status"][:EB] == 0).all()
+        runs[name] = (tr, states, out)
+    for name in ("double", "half", "zero"):
+        tr, states, out = runs[name]
+        ref = est_ref.run(tr, state=start)[0]
+        dx, dP = est_ref.worst_err(states, ref)
+        print(f"\nquaternion {name} on host threads: x {dx:.2e}, P {dP:.2e}")
+        assert dx <= X_BOUND and dP <= P_BOUND
+    normalised = est_ref.run(runs["given"][0], state=start)[0]
+    assert est_ref.worst_err(est_ref.run(runs["double"][0], state=start)[0], normalised)[0] >= 100 * X_BOUND
+    assert np.array_equal(kin_ref.quat2matrix_eigen(np.zeros((1, 4)))[0], np.eye(3))
+    assert est_ref.same_bits(runs["negated"][1][-1], runs["given"][1][-1])
+    assert est_ref.same_bits(runs["negated"][2]["root_states"][:EB, 3:7], -runs["given"][2]["root_states"][:EB, 3:7])
+
+
+@pytest.fixture(scope="module")
+def regimes():
+    """regime -> (trajectory, constants, batch-form records, d_x, d_P): the long regimes and
+    est_ref's own two forms on them."""
+    out = {}
+    for name in est_ref.D_REGIME:
+        traj, c = est_ref.regime_trajectory(EB, 200, name)
+        sb = est_ref.run(traj, c, "batch")[0]
+        out[name] = (traj, c, sb) + est_ref.worst_err(est_ref.run(traj, c, "sequential")[0], sb)
+    return out
+
+
+@pytest.mark.parametrize("name", list(est_ref.D_REGIME))
+def test_long_regimes_have_their_own_d(regimes, name):
+    """2g.  200 ticks of all-swing, all-stance and zero process noise: est_ref's two forms
+    differ by more than D_X / D_P there, so each regime records its own d (est_ref.D_REGIME),
+    measured here and printed."""
+    *_, dx, dP = regimes[name]
+    print(f"\nbatch vs sequential, {name}, {EB} robots x 200 ticks: d_x {dx:.3e}, d_P {dP:.3e}")
+    rx, rP = est_ref.D_REGIME[name]
+    assert dx <= rx <= 4 * dx and dP <= rP <= 4 * dP            # the recorded figures describe it
+
+
+@pytest.mark.parametrize("name", list(est_ref.D_REGIME))
+def test_host_kernel_long_regimes(kernel, regimes, name):
+    """2g on host threads: within 10 d of the batch form, P bitwise symmetric and finite,
+    status 0.  The regime matters: the generator's own trust and noise give records more
+    than 100 bounds away."""
+    traj, c, sb, *_ = regimes[name]
+    bx, bP = (10 * d for d in est_ref.D_REGIME[name])
+    st = np.zeros((EB, est_ref.STRIDE))
+    states, f32 = [st], 0.0
+    ref_out = est_ref.run(traj[:200], c)[1]
+    for i, inp in enumerate(traj):
+        full, out = host_tick(kernel, st, inp, constants=c)
+        st = full[:EB]
+        states.append(st)
+        P = est_ref.unpack(st)[1]
+        assert np.array_equal(P, np.swapaxes(P, 1, 2)) and np.isfinite(st).all() and (out["status"][:EB] == 0).all()
+        f32 = max([f32] + [est_ref.norm_err(out[k][b], ref_out[i][k][b]) for k in ("root_states", "feet_world") for b in range(EB)])
+    dx, dP = est_ref.worst_err(states, sb)
+    print(f"\n{name} on host threads: x {dx:.2e}, P {dP:.2e}, float32 outputs {f32:.2e}")
+    assert dx <= bx and dP <= bP and f32 <= max(F32_BOUND, bx)
+    plain = est_ref.run(est_ref.make_trajectory(EB, 200, seed=est_ref.REGIME_SEED))[0]
+    assert min(est_ref.worst_err(plain[:, b:b + 1], sb[:, b:b + 1])[1] for b in range(EB)) >= 100 * bP
+
+
+@pytest.mark.parametrize("B", [2, 5, 6])
+def test_host_kernel_batch_shapes(kernel, edge_start, B):
+    """2h.  An idle robot slot inside a workgroup (2, 5) and exactly full workgroups (6).  A
+    kernel that gave robot b the inputs of robot b - 1 would be out by more than 100 bounds."""
+    traj = [{k: v[:B] for k, v in t.items()} for t in edge_start[0][:10]]
+    ref = est_ref.run(traj)[0]
+    st = np.zeros((B, est_ref.STRIDE))
+    states = [st]
+    for inp in traj:
+        full, out = host_tick(kernel, st, inp)
+        st = full[:B]
+        states.append(st)
+        assert (out["status"][:B] == 0).all()
+    dx, dP = est_ref.worst_err(states, ref)
+    print(f"\nB = {B} on host threads: x {dx:.2e}, P {dP:.2e}")
+    assert dx <= X_BOUND and dP <= P_BOUND
+    assert est_ref.worst_err(ref[:, :B - 1], ref[:, 1:B])[0] >= 100 * X_BOUND

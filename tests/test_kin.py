@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import kin_edge_checks
 import kin_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -252,3 +253,43 @@ def test_leg_geometry_from_urdf(tmp_path):
         path = tmp_path / "short.urdf"
         path.write_text(kin_ref.urdf_text().replace("RL_foot_fixed", "RL_toe_fixed"))
         leg_geometry_from_urdf(str(path))
+
+
+# ---- the CPU twins of tests/test_gpu_kin_edges.py: the checks of tests/kin_edge_checks.py
+# on the host build of the header, its float64 outputs rounded to float32 as the kernel's
+# stores round them
+
+@pytest.fixture(scope="module")
+def edge_run(leg):
+    def run(geom, inp, layout, rot):
+        with np.errstate(all="ignore"):
+            out = run_header(leg, geom, rot=rot, **inp)
+            out = {k: np.concatenate([v.astype(np.float32), np.full((3,) + v.shape[1:], -77, np.float32)]) for k, v in out.items()}
+        return out
+    return run
+
+
+@pytest.mark.parametrize("layout", ["split", "rot"])
+def test_edge_poses(edge_run, leg, layout):
+    """4a on the host (the root layout is the split one to the header).  The header itself,
+    before the float32 store, is within 2.2e-16 of kin_ref."""
+    worst = kin_edge_checks.check_edge_poses(edge_run, layout)
+    print(f"\nedge poses on the host ({layout}), after the float32 store: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    geom, inp, rot = kin_ref.edge_poses()
+    rot = rot if layout == "rot" else None
+    errs = kin_ref.robot_errors(run_header(leg, geom, rot=rot, **inp), kin_ref.kinematics(geom, rot=rot, **inp))
+    rows = np.arange(len(geom)) != 9                     # zero geometry: exact zeros, no norm to divide by
+    f64 = max(float(np.nanmax(v[rows])) for v in errs.values())
+    print(f"header vs kin_ref in float64: {f64:.2e}")
+    assert f64 <= 1e-14
+    normalised, swapped = kin_edge_checks.wrong_reading_moves_the_result()
+    assert normalised >= 100 * kin_edge_checks.BOUND and swapped >= 100 * kin_edge_checks.BOUND
+
+
+def test_edge_nan_stays_where_the_algebra_puts_it(edge_run):
+    """4b on the host."""
+    seen = kin_edge_checks.check_nan_stays_put(edge_run, "split")
+    assert len(seen) == len(kin_ref.NAN_CASES)
+    for (key, idx), pattern in seen.items():
+        if key == "geom":
+            print(f"\nNaN in geom[{idx}]: " + ", ".join(sorted({k for k, _ in pattern})))
