@@ -252,7 +252,7 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
   // slack should not be the one to wait.  Each workgroup publishes (launch epoch, predicted
   // cost) -- prio_val, the dispatch order's key under the launch's epoch -- by an atomic max on
   // its CU's entry of the context's table, reads the entry back ahead of the H tile, and runs
-  // at priority 3 until the end of the sweep when the entry is its own.  The epoch makes
+  // at priority 3 through the sweep and its first passes of the active set when the entry is its own.  The epoch makes
   // earlier launches' entries lose, so the table is never cleared.  Wave 1 does both memory
   // operations: it waits for wave 0's model chain anyway, so the atomic and the load (issued
   // through form_model's pre_barrier, ~2 k cycles after the CU-mates, which start within ~1 us,
@@ -569,7 +569,12 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
   }
   STAMP(3);
   if constexpr (PRIO) {
-    if (prio_raised) __builtin_amdgcn_s_setprio(0);   // the setup priority ends with the sweep
+    // The priority is not dropped here, at the end of the sweep, but after the raised robot's
+    // first kPrioPasses passes of the active set (the loop's head): its CU-mates are still
+    // sweeping or in their own first passes then, and handing the SIMDs back at once cost the
+    // robot with no slack 8-12 k cycles of its active set.  Later the mates (a median robot
+    // makes 11 passes) are done or nearly so, and holding the priority to the end measured
+    // slower than 16 passes.
   }
 
   // unconstrained minimiser x = -W g
@@ -766,6 +771,8 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   };
+  constexpr int kPrioPasses = 16;
+  int prio_left = PRIO && prio_raised ? kPrioPasses : 0;   // passes left to begin at the setup priority
   bool early = false;   // kEarly: wave 1 already holds (and has published) the next choice
   int epc = -1, epc2 = -1;
   SEC(0);
@@ -848,6 +855,9 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
         tcA2 = (int)((unsigned)w0 / TW);   // w0 >= 0: shifts for TW = 8
         c02 = (int)((unsigned)w0 % TW);
       }
+    }
+    if constexpr (PRIO) {   // the setup priority ends with the raised robot's first passes
+      if (prio_left && --prio_left == 0) __builtin_amdgcn_s_setprio(0);
     }
     if (++it > max_iter) {
       status = MPCQP_STATUS_MAX_ITER;
@@ -1230,6 +1240,9 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
     SEC(0);
   }
   SEC(7);
+  if constexpr (PRIO) {   // a raised robot that ended within its first passes
+    if (prio_left) __builtin_amdgcn_s_setprio(0);
+  }
   STAMP(4);
 
   // ------------------------------- final x, KKT verification, output

@@ -8,6 +8,8 @@ GI step).  Decisions follow the engine: the most violated row in the dual metric
 (scaled by the initial W), partner rows the best of other foot-steps.
 Usage: python tools/gi_sim.py [B] [k ...]   (GI_METRIC=W: rows keyed in the initial metric;
 GI_N / GI_GAITS: horizon and gait mix, default 10 / trot10)
+       python tools/gi_sim.py [B] merge     (class 64's exchange pass: simulate(..., merge=True) finishes
+a dropped slot's pending row in the drop's own pass; the pass counts with and without, per bench.py batch)
 """
 import os
 import sys
@@ -55,7 +57,12 @@ def robot_qp(bt, b, N):
 
 
 def simulate(H, g, A, b, foot, kmax, tol=1e-9, max_pass=2000, ratio=0.0, stop_after_drops=10**9, W0=None,
-             metric="P", init_rows=None):
+             metric="P", init_rows=None, merge=False):
+    """merge: after a drop, take the pending row's step in the same pass when that step is an add
+    (class 64's exchange pass); the decisions, iterations and drops are those of the two passes it
+    replaces.  The result's `kinds` counts passes per kind (pairs / adds / drops / merged) and
+    `events` lists every pass as (iterations before the pass, kind, dropped slot or -1, (first) slot
+    a row went into or -1, occupied slots before the pass), kind one of pair / add / drop / merged."""
     n = H.shape[0]
     W = np.linalg.inv(H) if W0 is None else W0.copy()
     P = W.copy()
@@ -82,6 +89,8 @@ def simulate(H, g, A, b, foot, kmax, tol=1e-9, max_pass=2000, ratio=0.0, stop_af
     rn = 1.0 / np.sqrt(np.einsum("ij,jk,ik->i", A, W, A))
     wscale = np.max(np.diag(W))
     passes = it = drops = multi = 0
+    kinds = dict(pairs=0, adds=0, drops=0, merged=0)
+    events = []
     cost = 0.0   # crude per-pass cost model (single-add pass = 1)
     p = -1
     up = 0.0
@@ -150,6 +159,8 @@ def simulate(H, g, A, b, foot, kmax, tol=1e-9, max_pass=2000, ratio=0.0, stop_af
                     u[q] = t[j]
                 it += k
                 multi += k > 1
+                kinds["pairs" if k > 1 else "adds"] += 1
+                events.append((it - k, "pair" if k > 1 else "add", -1, int(free[0]), int(occ.sum()) - k))
                 cost += 0.2 * k   # rank-k update beyond the rank-1 of a single add
                 p = -1
                 done = True
@@ -168,7 +179,8 @@ def simulate(H, g, A, b, foot, kmax, tol=1e-9, max_pass=2000, ratio=0.0, stop_af
         t2 = -sp / zsp if zsp > thr else np.inf
         tstep = min(t1, t2)
         if not np.isfinite(tstep):
-            return dict(passes=passes, it=it, drops=drops, multi=multi, status="infeasible")
+            return dict(passes=passes, it=it, drops=drops, multi=multi, status="infeasible", kinds=kinds,
+                        events=events)
         if np.isfinite(t2):
             x = x + tstep * z
         u = np.where(occ, u - tstep * r, u)
@@ -183,7 +195,10 @@ def simulate(H, g, A, b, foot, kmax, tol=1e-9, max_pass=2000, ratio=0.0, stop_af
             slot_row[q] = p
             u[q] = up
             p = -1
+            kinds["adds"] += 1
+            events.append((it - 1, "add", -1, q, int(occ.sum()) - 1))
         else:
+            nocc = int(occ.sum())
             Rl = R[l].copy()
             y = R @ (H @ Rl)
             eta = y[l]
@@ -195,14 +210,66 @@ def simulate(H, g, A, b, foot, kmax, tol=1e-9, max_pass=2000, ratio=0.0, stop_af
             u[l] = 0.0
             drops += 1
             cost += 0.6   # H R_l, R (H R_l): two matvecs, two more barriers
+            q = -1
+            if merge:
+                # the pending row's step on the updated P, R: the next pass's, taken here when it adds
+                z = P @ A[p]
+                r = R @ A[p]
+                zsp = A[p] @ z
+                sp = A[p] @ x - b[p]
+                ratios = np.where(occ & (r > 0), u / np.where(r > 0, r, 1), np.inf)
+                t1 = ratios[int(np.argmin(ratios))]
+                t2 = -sp / zsp if zsp > thr else np.inf
+                if t2 <= t1 and np.isfinite(t2):
+                    it += 1
+                    x = x + t2 * z
+                    u = np.where(occ, u - t2 * r, u)
+                    up += t2
+                    q = int(np.flatnonzero(~occ)[0])
+                    e = np.zeros(n)
+                    e[q] = 1.0
+                    P = P - np.outer(z, z) / zsp
+                    R = R - np.outer(r - e, z) / zsp
+                    occ[q] = True
+                    slot_row[q] = p
+                    u[q] = up
+                    p = -1
+                    cost += 0.4   # no combo, barrier or zs for the add
+            kinds["merged" if q >= 0 else "drops"] += 1
+            events.append((it - (2 if q >= 0 else 1), "merged" if q >= 0 else "drop", l, q, nocc))
     return dict(passes=passes, it=it, drops=drops, multi=multi, x=x, cost=cost, active=sorted(slot_row[occ].tolist()),
-                u=u[occ])
+                u=u[occ], kinds=kinds, events=events)
+
+
+def merge_table(B, N, gaits, seeds=(1000, 2000, 3000, 4000)):
+    """Pair steps (the engine's loop) with and without the exchange pass on the batches bench.py
+    cycles: the slowest robot's passes and pass kinds, as a markdown table."""
+    print("| seed | max passes, now | max passes, merged | slowest robot now: pairs / adds / drops |"
+          " same robot merged: pairs / adds / drops / merged passes | mean passes now / merged |"
+          " iterations, drops unchanged |")
+    print("|---|---|---|---|---|---|---|")
+    for seed in seeds:
+        bt = make_batch(B, N, seed=seed, gaits=gaits, robots=("a1",))
+        qps = [robot_qp(bt, b, N) for b in range(B)]
+        now = [simulate(*qp, kmax=2) for qp in qps]
+        mer = [simulate(*qp, kmax=2, merge=True) for qp in qps]
+        pn = np.array([r["passes"] for r in now])
+        pm = np.array([r["passes"] for r in mer])
+        w = int(np.argmax(pn))
+        kn, km = now[w]["kinds"], mer[w]["kinds"]
+        same = all(a["it"] == c["it"] and a["drops"] == c["drops"] for a, c in zip(now, mer))
+        print(f"| {seed} | {pn.max()} (robot {w}) | {pm.max()} | {kn['pairs']} / {kn['adds']} / {kn['drops']} |"
+              f" {km['pairs']} / {km['adds']} / {km['drops']} / {km['merged']} | {pn.mean():.1f} / {pm.mean():.1f} |"
+              f" {'yes' if same else 'NO'} (max {max(r['it'] for r in now)}) |")
 
 
 def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-    ks = [a for a in sys.argv[2:]] or ["1", "2", "3", "4"]
     N = int(os.environ.get("GI_N", "10"))   # GI_N=16 GI_GAITS=trot10,pace10,bound8: the config-4 mix
+    if "merge" in sys.argv[2:]:   # python tools/gi_sim.py 1024 merge: the exchange pass's table
+        merge_table(B, N, tuple(os.environ.get("GI_GAITS", "trot10").split(",")))
+        return
+    ks = [a for a in sys.argv[2:]] or ["1", "2", "3", "4"]
     bt = make_batch(B, N, seed=1000, gaits=tuple(os.environ.get("GI_GAITS", "trot10").split(",")), robots=("a1",))
     qps = [robot_qp(bt, b, N) for b in range(B)]
     ref = None
