@@ -32,7 +32,11 @@
  *                     (mpc.py:65-77; x0[2] is also the model yaw, mpc.py:77)
  *   xref    [B][N][13] reference of x_{1..N} (mpc.py:154-168)
  *   contact [B][N][4]  legs FL, FR, RL, RR; > 0 = stance (gait.py:87-98);
- *                      ub of the normal-force row is contact * fz_max (mpc.py:257)
+ *                      ub of the normal-force row is contact * fz_max (mpc.py:257), so a
+ *                      value other than 1 scales the foot-step's bound.  Anything that is
+ *                      not > 0 is swing: 0, a negative value, -inf and NaN alike (the
+ *                      values are not otherwise checked).  +inf would be an infinite
+ *                      bound: the robot is refused (MPCQP_STATUS_NONFINITE)
  *   feet    [B][4][3]  foot position relative to the CoM, world frame
  *                      (RobotData.pos_base_feet, robot_data.py:101,144-149)
  *   robot   [B][16]    per-robot record: mass, ixx, ixy, ixz, iyy, iyz, izz,
@@ -41,7 +45,9 @@
  *   u0      [B][12]    out: first-step GRFs, world frame (mpc.py:99)
  *   U       [B][N][12] out (nullable): the whole optimal input sequence
  *   status  [B]        out (nullable): MPCQP_STATUS_*
- *   iters   [B]        out (nullable): active-set steps executed (a pair step counts 2);
+ *   iters   [B]        out (nullable): active-set steps executed (a pair step counts 2, so
+ *                      under MPCQP_STATUS_MAX_ITER at most max_iter + 1: a pass refused at
+ *                      the cap is not counted);
  *                      for a robot with more than 128 stance variables (the interior-point
  *                      class: standing schedules at N >= 11) the Newton factorisations
  *
@@ -82,7 +88,10 @@ extern "C" {
 #define MPCQP_STATUS_MAX_ITER 1    /* iteration cap hit: best iterate returned */
 #define MPCQP_STATUS_INFEASIBLE 2  /* cannot happen for this QP (U = 0 is feasible) */
 #define MPCQP_STATUS_TOO_LARGE 3   /* stance variables exceed the engine's capacity */
-#define MPCQP_STATUS_NONFINITE 4   /* non-finite input or result */
+#define MPCQP_STATUS_NONFINITE 4   /* non-finite input (x0, xref, feet, robot[0..11]; a +inf
+                                      contact) or result (finite inputs reach it: mass 0, a
+                                      singular inertia, a surface normal along world x, whose
+                                      tangent frame is 0 / 0); u0 / U are 0, iters 0 */
 #define MPCQP_STATUS_UNSUPPORTED 5 /* weights the robot's capacity class cannot apply; no
                                       weights reach it since ABI 6's cross-leg stage weights
                                       (kept as a guard); u0 / U are 0 */

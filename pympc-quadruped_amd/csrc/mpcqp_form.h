@@ -95,7 +95,8 @@ __device__ __forceinline__ bool fany(bool v) {
   else return __syncthreads_or(v) != 0;
 }
 
-// Stage the robot's inputs in LDS; false if any is non-finite (status NONFINITE).
+// Stage the robot's inputs in LDS; false if any is non-finite, or a contact value is +inf
+// (status NONFINITE).
 // `pre` (class 64): work that needs none of the inputs, run between the issue of a thread's
 // first chunk load and its use, i.e. under the global-load latency.
 struct StageNoPre {
@@ -146,7 +147,9 @@ __device__ __forceinline__ bool form_stage(F& f, int N, int b, int tid, const fl
       const int kk = k.e + j;
       if (kk >= 0 && kk < len) {
         in[dst + kk] = w;
-        bad |= i != 3 && !isfinite(w);   // contact is not checked
+        // contact: NaN and anything <= 0 (-inf too) mean swing (form_stance); only +inf, an
+        // infinite fz bound, is refused
+        bad |= i == 3 ? w == INFINITY : !isfinite(w);
       }
     }
   };

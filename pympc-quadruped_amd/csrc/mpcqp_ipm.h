@@ -1397,8 +1397,13 @@ __device__ __forceinline__ void solve_robot_ipm(const KParams& KP, int b, IpmSha
 
   // ------------------------------------------------ output (the polished optimum or the last iterate)
   bool finite = true;
-  for (int e = lane; e < N * NU; e += NT) finite &= isfinite(sm.U[e / NU][e % NU]);
-  if (__any(!finite)) status = MPCQP_STATUS_NONFINITE;
+  for (int e = lane; e < N * NU; e += NT) finite &= isfinite((float)sm.U[e / NU][e % NU]);   // as stored below
+  if (__any(!finite)) {   // reported as such, with u0 / U = 0 like a non-finite input: no NaN leaves the solve
+    status = MPCQP_STATUS_NONFINITE;
+    nfact = 0;
+    for (int e = lane; e < N * NU; e += NT) sm.U[e / NU][e % NU] = 0.0;
+    fsync<NT>();
+  }
   if (lane < 12) u0g[(size_t)b * 12 + lane] = (float)sm.U[0][lane];
   if (wmem) {   // remember the verified set (0x80 | rows; swing foot-steps 0x80), or nothing
     const bool ok = status == MPCQP_STATUS_OK;

@@ -860,6 +860,7 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
       if (prio_left && --prio_left == 0) __builtin_amdgcn_s_setprio(0);
     }
     if (++it > max_iter) {
+      --it;   // the refused pass is not a step executed: iters <= max_iter + 1 (a pair step begun at the cap)
       status = MPCQP_STATUS_MAX_ITER;
       break;
     }
@@ -1252,19 +1253,28 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
     for (int k = 0; k < VPL; ++k) sm.vx[lane + LANES * k] = x[k];
   }
   fsync<NT>();
+  bool nonfinite = false;
   {
-    int bad = 0;
+    int bad = 0;   // bit 0: a KKT condition fails; bit 1: a non-finite row value or result
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
       if (lane + LANES * k < m) {
         const double v = cdot(sm.vx, k) + cbound(k);
-        bad |= (v < -1e-6) || !isfinite(v);
+        bad |= (v < -1e-6) | (isfinite(v) ? 0 : 2);
       }
     }
 #pragma unroll
-    for (int k = 0; k < VPL; ++k)
+    for (int k = 0; k < VPL; ++k) {
       if ((occ[k] >> lane) & 1ull) bad |= (u[k] < -1e-9);
-    if (__any(bad) && status == MPCQP_STATUS_OK) status = MPCQP_STATUS_MAX_ITER;
+      // the result itself, as the float32 the store below would write (every variable is also
+      // in a cone row with a non-zero coefficient, so v above catches a non-finite x as well)
+      if (lane + LANES * k < n) bad |= isfinite((float)sm.vx[lane + LANES * k]) ? 0 : 2;
+    }
+    // A non-finite cone row or result (finite inputs reach it: mass 0, a singular inertia, a
+    // surface normal along world x) is reported as such with u0 / U = 0, never handed on as a
+    // "best iterate".  Every wave holds the same vx, rows and bounds: the decision is uniform.
+    nonfinite = __any(bad & 2) != 0;
+    if (__any(bad & 1) && status == MPCQP_STATUS_OK) status = MPCQP_STATUS_MAX_ITER;
   }
   STAMP(5);
   STAMP(6);
@@ -1290,6 +1300,10 @@ __device__ __forceinline__ void solve_robot(const KParams& P, int b, SharedT<NV>
   }
   Ug = nullptr;
 #endif
+  if (nonfinite) {
+    write_empty_t<NT>(b, tid, N, MPCQP_STATUS_NONFINITE, u0g, Ug, statusg, itersg);
+    return;
+  }
   if (wave == 0) {
     if (lane < 12) {
       const int sidx = sm.mt.stance_of[lane / 3];

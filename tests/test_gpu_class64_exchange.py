@@ -106,12 +106,13 @@ def _small_case():
 def _expected_under_cap(events, total, cap):
     """Status and reported count under max_iter = cap by the rule at the loop's head (a pass
     starts only while the count after it is begun stays within the cap; a cap between a drop
-    and its add lets the drop through and refuses the add, merged into one pass or not)."""
+    and its add lets the drop through and refuses the add, merged into one pass or not).  The
+    count is the steps executed (include/mpcqp.h): the refused pass is not one of them."""
     for before, kind, _, _, _ in events:
         if before + 1 > cap:
-            return STATUS_MAX_ITER, before + 1
+            return STATUS_MAX_ITER, before
         if kind == "merged" and before + 1 == cap:
-            return STATUS_MAX_ITER, cap + 1
+            return STATUS_MAX_ITER, cap
     return STATUS_OK, total
 
 
@@ -143,7 +144,7 @@ def test_cases_are_what_they_claim():
     between = [e[0] + 1 for e in _merged(r)]   # the caps that fall between a drop and its add
     assert between and r["events"][-1][1] != "pair"
     for cap in between:
-        assert _expected_under_cap(r["events"], r["it"], cap) == (STATUS_MAX_ITER, cap + 1)
+        assert _expected_under_cap(r["events"], r["it"], cap) == (STATUS_MAX_ITER, cap)
     assert _expected_under_cap(r["events"], r["it"], r["it"]) == (STATUS_OK, r["it"])
     assert all(_expected_under_cap(r["events"], r["it"], cap)[0] == STATUS_MAX_ITER for cap in range(1, r["it"]))
 
