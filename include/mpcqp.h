@@ -357,6 +357,54 @@ int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, c
                                  float* pos_feet, float* foot_pos_base, float* foot_vel_base, float* jac,
                                  void* stream);
 
+/* ---- the control tick in one call: kinematics, plan and leg torques fused ----
+ *
+ * mpcqp_step is the whole loop body of scripts/isaacgym_a1.py:117-162 for B robots on the
+ * simulator's two state tensors: what mpcqp_kinematics_root_states, mpcqp_plan_root_states,
+ * (on an MPC tick) mpcqp_solve and mpcqp_leg_torques_root_states do when issued in that order
+ * on the same buffers, and bitwise their results.  Isaac Gym layout only; a caller with
+ * split arrays keeps those entry points.  No allocation beyond what mpcqp_solve makes on its
+ * first use, no synchronisation or host read.
+ *
+ *   flags        0: a tick between two solves (mpc.py:95-106 holds u0) -- ONE launch; the
+ *                        kinematic arrays stay in registers unless asked for.
+ *                MPCQP_STEP_MPC when iter % iterations_between_mpc == 0 (mpc.py:95; the caller
+ *                        decides, as with MPCQP_PLAN_REFERENCE): one call that enqueues, on
+ *                        `stream`, the kinematics and the plan with the reference, exactly what
+ *                        mpcqp_solve enqueues (warm start, order, stance range and weights
+ *                        apply), and the leg controller on the fresh u0.
+ *   iter_counter, tick   the control-iteration counter (isaacgym_a1.py:137): tick [B] int32 is
+ *                        each robot's, as for mpcqp_leg_torques; with tick == NULL every robot
+ *                        uses iter_counter.  On an MPC tick the gait table starts at segment
+ *                        floor(tick / iterations_between_mpc) mod period (gait.py:76-78).
+ *   iterations_between_mpc   linear_mpc_configs.py:7 (20); >= 1
+ *   root_states  [B][13], dof_states [B][12][2]   as for mpcqp_kinematics_root_states
+ *   geom         as for mpcqp_kinematics
+ *   vel_body_des, yaw_rate_des, gait (required), height_des   as for mpcqp_plan
+ *   robot        as for mpcqp_solve
+ *   plan_state, x0, xref, contact   in/out and out, as for mpcqp_plan
+ *   swing_mem    in/out, 16-byte aligned, as for mpcqp_leg_torques
+ *   feet         [B][4][3]  out: the `feet` the solve reads (nullable with flags == 0)
+ *   u0           [B][12]  in with flags == 0 (the forces of the last solve), out and in with
+ *                        MPCQP_STEP_MPC
+ *   tau          [B][12]  out, as for mpcqp_leg_torques
+ *   status, iters   out (nullable), as for mpcqp_solve; written on an MPC tick only
+ *   thighs, pos_feet, foot_pos_base, foot_vel_base, jac   out (nullable), as for mpcqp_kinematics
+ *   swing_state, pos_target, vel_target   out (nullable), as for mpcqp_leg_torques
+ * With flags == 0, xref, contact, feet, robot, height_des, status and iters may be NULL (none is
+ * touched).  MPCQP_ERR_ARG, with nothing written, for unknown flags, batch < 0,
+ * iterations_between_mpc < 1, a NULL required pointer (xref, contact, feet, robot and
+ * height_des among them with MPCQP_STEP_MPC) and a swing_mem that is not 16-byte aligned;
+ * batch == 0 is MPCQP_OK.  The constants are those of mpcqp_set_planner and mpcqp_set_swing. */
+#define MPCQP_STEP_MPC 1
+int mpcqp_step(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t iter_counter, const int32_t* tick,
+               int32_t iterations_between_mpc, const float* root_states, const float* dof_states,
+               const double* geom, const double* vel_body_des, const double* yaw_rate_des, const int32_t* gait,
+               const float* height_des, const float* robot, double* plan_state, double* swing_mem, float* x0,
+               float* xref, float* contact, float* feet, float* u0, float* tau, int32_t* status, int32_t* iters,
+               float* thighs, float* pos_feet, float* foot_pos_base, float* foot_vel_base, float* jac,
+               float* swing_state, float* pos_target, float* vel_target, void* stream);
+
 /* ---- the base-state estimator on the device: IMU + leg-kinematics Kalman filter ----
  *
  * mpcqp_estimate is one tick, for B robots in one launch, of the linear Kalman filter the

@@ -351,6 +351,7 @@ constexpr int kPrioTab = 4096;
 #include "mpcqp_plan.h"
 #include "mpcqp_swing.h"
 #include "mpcqp_kinematics.h"
+#include "mpcqp_step.h"
 #include "mpcqp_estimator.h"
 #include "mpcqp_attitude.h"
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
@@ -921,16 +922,11 @@ int mpcqp_set_stance_range(mpcqp_ctx* ctx, int32_t min_stance, int32_t max_stanc
   return MPCQP_OK;
 }
 
-int mpcqp_solve(mpcqp_ctx* ctx, int32_t batch, const float* x0, const float* xref, const float* contact,
-                const float* feet, const float* robot, float* u0, float* U, int32_t* status, int32_t* iters,
-                void* stream) {
-  if (!ctx) return MPCQP_ERR_ARG;
-  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "batch < 0");
-  if (batch == 0) return MPCQP_OK;
-  if (!x0 || !xref || !contact || !feet || !robot || !u0)
-    return set_err(ctx, MPCQP_ERR_ARG, "null input/output pointer");
-  DeviceScope dev(ctx->device);
-  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+// Everything mpcqp_solve enqueues on `stream`, for mpcqp_solve and mpcqp_step: the arguments are
+// checked (batch > 0, no NULL required pointer) and the context's device is current.
+static int enqueue_solve(mpcqp_ctx* ctx, int32_t batch, const float* x0, const float* xref, const float* contact,
+                         const float* feet, const float* robot, float* u0, float* U, int32_t* status,
+                         int32_t* iters, void* stream) {
   KParams kp;
   kp.N = ctx->params.horizon;
   kp.max_iter = ctx->params.max_iter;
@@ -1098,6 +1094,19 @@ int mpcqp_solve(mpcqp_ctx* ctx, int32_t batch, const float* x0, const float* xre
   }
   if (qs && hipEventRecord(qs->ev_done, st) != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, "queue event record failed");
   return MPCQP_OK;
+}
+
+int mpcqp_solve(mpcqp_ctx* ctx, int32_t batch, const float* x0, const float* xref, const float* contact,
+                const float* feet, const float* robot, float* u0, float* U, int32_t* status, int32_t* iters,
+                void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "batch < 0");
+  if (batch == 0) return MPCQP_OK;
+  if (!x0 || !xref || !contact || !feet || !robot || !u0)
+    return set_err(ctx, MPCQP_ERR_ARG, "null input/output pointer");
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  return enqueue_solve(ctx, batch, x0, xref, contact, feet, robot, u0, U, status, iters, stream);
 }
 
 int mpcqp_set_weights(mpcqp_ctx* ctx, const double* Q, const double* R) {
@@ -1365,6 +1374,61 @@ int mpcqp_kinematics_root_states(mpcqp_ctx* ctx, int32_t batch, int32_t flags, c
                                  void* stream) {
   return launch_kinematics(ctx, batch, flags, 1, root_states, nullptr, nullptr, nullptr, nullptr, dof_states,
                            nullptr, geom, feet, thighs, pos_feet, foot_pos_base, foot_vel_base, jac, stream);
+}
+
+// ---- the control tick in one call (mpcqp_step.h; isaacgym_a1.py:117-162): one STEP_WHOLE
+// launch, or on an MPC tick STEP_FRONT, what mpcqp_solve enqueues and STEP_BACK
+int mpcqp_step(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t iter_counter, const int32_t* tick,
+               int32_t iterations_between_mpc, const float* root_states, const float* dof_states,
+               const double* geom, const double* vel_body_des, const double* yaw_rate_des, const int32_t* gait,
+               const float* height_des, const float* robot, double* plan_state, double* swing_mem, float* x0,
+               float* xref, float* contact, float* feet, float* u0, float* tau, int32_t* status, int32_t* iters,
+               float* thighs, float* pos_feet, float* foot_pos_base, float* foot_vel_base, float* jac,
+               float* swing_state, float* pos_target, float* vel_target, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "batch < 0");
+  if (flags & ~MPCQP_STEP_MPC) return set_err(ctx, MPCQP_ERR_ARG, "unknown step flags");
+  if (iterations_between_mpc < 1) return set_err(ctx, MPCQP_ERR_ARG, "iterations_between_mpc < 1");
+  if (batch == 0) return MPCQP_OK;
+  if (!root_states || !dof_states || !geom || !vel_body_des || !yaw_rate_des || !gait || !plan_state ||
+      !swing_mem || !x0 || !u0 || !tau)
+    return set_err(ctx, MPCQP_ERR_ARG, "null step input/output pointer");
+  const bool mpc = (flags & MPCQP_STEP_MPC) != 0;
+  if (mpc && (!height_des || !robot || !xref || !contact || !feet))
+    return set_err(ctx, MPCQP_ERR_ARG, "null height/robot/xref/contact/feet pointer on an MPC tick");
+  if ((uintptr_t)swing_mem & 15) return set_err(ctx, MPCQP_ERR_ARG, "swing_mem is not 16-byte aligned");
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  StepParams sp;
+  sp.N = ctx->params.horizon;
+  sp.dt = ctx->params.dt;
+  sp.max_pos_error = ctx->max_pos_error;
+  sp.sw.ibm = iterations_between_mpc;
+  sp.sw.root_layout = 1;
+  sp.sw.dt_control = ctx->dt_control;
+  sp.sw.gravity = ctx->gravity;
+  sp.sw.swing_height = ctx->swing_height;
+  sp.sw.touchdown_z = ctx->touchdown_z;
+  sp.sw.vel_gain = ctx->vel_gain;
+  memcpy(sp.sw.Kp, ctx->kp_swing, sizeof(sp.sw.Kp));
+  memcpy(sp.sw.Kd, ctx->kd_swing, sizeof(sp.sw.Kd));
+  const dim3 grid((batch + kStepRobots - 1) / kStepRobots), block(kStepThreads);
+  hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto kern, const char* what) -> int {
+    hipLaunchKernelGGL(kern, grid, block, 0, st, sp, (int)batch, (int)iter_counter, tick, root_states, dof_states,
+                       geom, vel_body_des, yaw_rate_des, gait, height_des, plan_state, swing_mem, x0, xref, contact,
+                       feet, (const float*)u0, tau, thighs, pos_feet, foot_pos_base, foot_vel_base, jac,
+                       swing_state, pos_target, vel_target);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string(what) + hipGetErrorString(e));
+    return MPCQP_OK;
+  };
+  if (!mpc) return launch(mpcqp_step_kernel<STEP_WHOLE>, "step launch: ");
+  int rc = launch(mpcqp_step_kernel<STEP_FRONT>, "step launch (front): ");
+  if (rc != MPCQP_OK) return rc;
+  rc = enqueue_solve(ctx, batch, x0, xref, contact, feet, robot, u0, nullptr, status, iters, stream);
+  if (rc != MPCQP_OK) return rc;
+  return launch(mpcqp_step_kernel<STEP_BACK>, "step launch (back): ");
 }
 
 // ---- the base-state estimator (mpcqp_estimator.h): the Kalman filter doc/state_estimation_kf.md

@@ -60,147 +60,130 @@ __device__ inline void plan_quat2matrix(float qw, float qx, float qy, float qz, 
   R[8] = (((ww - xx) - yy) + zz);
 }
 
-__global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
-    PlanParams pp, int B, const float* __restrict__ quat, const float* __restrict__ pos,
-    const float* __restrict__ omega, const float* __restrict__ vel, const float* __restrict__ rot,
-    const double* __restrict__ vbody, const double* __restrict__ yaw_rate, const int* __restrict__ gait,
-    const int* __restrict__ iteration, const float* __restrict__ height, double* __restrict__ state,
-    float* __restrict__ x0, float* __restrict__ xref, float* __restrict__ contact) {
+// Phase 1 for robot b, on one lane: pack the state into x0, run the desired-pose integrators
+// and, on an MPC tick, clamp, compensate and leave the robot's row seeds in `sd` (one text for
+// mpcqp_plan_kernel and mpcqp_step_kernel).  The state inputs are the robot's float32 values;
+// `rot` is the caller's R_base [B][9] or NULL.  The gait segment is iteration[b], or `ih0`
+// when `iteration` is NULL (mpcqp_step_kernel derives it from the robot's tick).
+__device__ inline void plan_robot(const PlanParams& pp, int b, float qw, float qx, float qy, float qz,
+                                  const float (&p3)[3], const float (&w3)[3], const float (&v3)[3],
+                                  const float* __restrict__ rot, const double* __restrict__ vbody,
+                                  const double* __restrict__ yaw_rate, const int* __restrict__ gait,
+                                  const int* __restrict__ iteration, int ih0, const float* __restrict__ height,
+                                  double* __restrict__ state, float* __restrict__ x0, PlanSeed& sd) {
 #pragma clang fp contract(off)   // every product and sum rounds, as in NumPy
-  __shared__ PlanSeed seed[kPlanRobots];
-  __shared__ float seq[kPlanRobots][3][kMaxN];   // yaw / x / y along the horizon
-  const int N = pp.N;
-  const int b0 = blockIdx.x * kPlanRobots;
-  const int nrob = min(kPlanRobots, B - b0);
-  const int t = threadIdx.x;
-
-  if (t < nrob) {
-    const int b = b0 + t;
-    // ---- inputs: separate arrays, or one Isaac Gym actor-root-state row
-    // [pos(3), quat(x, y, z, w), lin_vel(3), ang_vel(3)] (isaacgym_a1.py:119-128)
-    float qw, qx, qy, qz, p3[3], w3[3], v3[3];
-    if (pp.root_layout) {
-      const float* rs = quat + (size_t)b * 13;
-      qx = rs[3], qy = rs[4], qz = rs[5], qw = rs[6];
+  // ---- pack the state (mpc.py:64-76).  quat2ZYXangle (kinematics.py:40-49) on a
+  // float32 quaternion: NumPy float32 scalar products and sums, each rounded (the
+  // contract(off) pragma above keeps them unfused), then math.atan2 / asin in float64
+  const float a_r = 2.f * ((qw * qx) + (qy * qz));
+  const float b_r = (1.f - 2.f * ((qx * qx) + (qy * qy)));
+  const float a_p = 2.f * ((qw * qy) - (qz * qx));
+  const float a_y = 2.f * ((qw * qz) + (qx * qy));
+  const float b_y = (1.f - 2.f * ((qy * qy) + (qz * qz)));
+  const double roll = atan2((double)a_r, (double)b_r);
+  // math.asin raises past +-1 instead; the comparisons (not fmin / fmax, which drop a
+  // NaN for the bound) let a NaN quaternion give a NaN pitch, like its roll and yaw
+  const double s_p = (double)a_p;
+  const double pitch = asin(s_p > 1.0 ? 1.0 : (s_p < -1.0 ? -1.0 : s_p));
+  const double yaw = atan2((double)a_y, (double)b_y);
+  float xs[NX];
+  xs[0] = (float)roll;
+  xs[1] = (float)pitch;
+  xs[2] = (float)yaw;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        p3[k] = rs[k];
-        v3[k] = rs[7 + k];
-        w3[k] = rs[10 + k];
-      }
-    } else {
-      qw = quat[4 * b], qx = quat[4 * b + 1], qy = quat[4 * b + 2], qz = quat[4 * b + 3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        p3[k] = pos[3 * b + k];
-        w3[k] = omega[3 * b + k];
-        v3[k] = vel[3 * b + k];
-      }
-    }
-    // ---- pack the state (mpc.py:64-76).  quat2ZYXangle (kinematics.py:40-49) on a
-    // float32 quaternion: NumPy float32 scalar products and sums, each rounded (the
-    // contract(off) pragma above keeps them unfused), then math.atan2 / asin in float64
-    const float a_r = 2.f * ((qw * qx) + (qy * qz));
-    const float b_r = (1.f - 2.f * ((qx * qx) + (qy * qy)));
-    const float a_p = 2.f * ((qw * qy) - (qz * qx));
-    const float a_y = 2.f * ((qw * qz) + (qx * qy));
-    const float b_y = (1.f - 2.f * ((qy * qy) + (qz * qz)));
-    const double roll = atan2((double)a_r, (double)b_r);
-    // math.asin raises past +-1 instead; the comparisons (not fmin / fmax, which drop a
-    // NaN for the bound) let a NaN quaternion give a NaN pitch, like its roll and yaw
-    const double s_p = (double)a_p;
-    const double pitch = asin(s_p > 1.0 ? 1.0 : (s_p < -1.0 ? -1.0 : s_p));
-    const double yaw = atan2((double)a_y, (double)b_y);
-    float xs[NX];
-    xs[0] = (float)roll;
-    xs[1] = (float)pitch;
-    xs[2] = (float)yaw;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      xs[3 + k] = p3[k];
-      xs[6 + k] = w3[k];
-      xs[9 + k] = v3[k];
-    }
-    xs[12] = (float)(-pp.gravity);
-#pragma unroll
-    for (int k = 0; k < NX; ++k) x0[(size_t)b * NX + k] = xs[k];
-
-    // ---- desired velocity in the world frame: R_base @ v_body (mpc.py:83).  Without
-    // a caller-supplied R_base it is quat2matrix(quat) (robot_data.py:75,
-    // kinematics.py:51-71) in the same float32 scalar arithmetic
-    float R[9];
-    if (rot != nullptr) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) R[k] = rot[9 * b + k];
-    } else {
-      plan_quat2matrix(qw, qx, qy, qz, R);
-    }
-    // the body-frame command is float64 (a Python list / float64 array in the scripts)
-    double vdes[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      vdes[r] = (double)R[3 * r] * vbody[3 * b] + (double)R[3 * r + 1] * vbody[3 * b + 1] +
-                (double)R[3 * r + 2] * vbody[3 * b + 2];
-    const double rate = yaw_rate[b];
-
-    // ---- pose integrators (mpc.py:84-92); the yaw is self.yaw = rpy[2] in float64
-    double* st = state + (size_t)b * 8;
-    const bool started = st[PL_STARTED] != 0.0;
-    double xd, yd, yawd;
-    if (pp.integrate) {
-      xd = started ? st[PL_X] + pp.dt_control * vdes[0] : 0.0;
-      yd = started ? st[PL_Y] + pp.dt_control * vdes[1] : 0.0;
-      yawd = started ? yaw + pp.dt_control * rate : yaw;
-    } else {   // generate_reference_trajectory alone (mpc.py:110) reads the last integration
-      xd = st[PL_X];
-      yd = st[PL_Y];
-      yawd = started ? st[PL_YAW] : yaw;
-    }
-    double roll_init = started ? st[PL_ROLL] : 0.0;
-    double pitch_init = started ? st[PL_PITCH] : 0.0;
-
-    if (pp.mpc_tick) {
-      // ---- position clamp (mpc.py:121-140)
-      const double px = xs[3], py = xs[4], e = pp.max_pos_error;
-      if (xd - px > e) xd = px + e;
-      if (px - xd > e) xd = px - e;
-      if (yd - py > e) yd = py + e;
-      if (py - yd > e) yd = py - e;
-      // ---- roll / pitch compensation (mpc.py:143-152), NumPy 1.x promotion: float64
-      const double vx = xs[9], vy = xs[10];
-      if (fabs(vx) > 0.2) pitch_init += pp.dt * (0.0 - (double)xs[1]) / vx;
-      if (fabs(vy) > 0.1) roll_init += pp.dt * (0.0 - (double)xs[0]) / vy;
-      roll_init = fmin(fmax(roll_init, -0.25), 0.25);
-      pitch_init = fmin(fmax(pitch_init, -0.25), 0.25);
-      PlanSeed& sd = seed[t];
-      sd.rate = rate;
-      sd.vx = vdes[0];
-      sd.vy = vdes[1];
-      sd.yawd = yawd;
-      sd.xd = xd;
-      sd.yd = yd;
-      sd.roll_comp = (float)(vy * roll_init);
-      sd.pitch_comp = (float)(vx * pitch_init);
-      sd.height = height[b];
-      if (gait != nullptr) {
-        const int* gs = gait + 9 * b;   // period, offsets[4], durations[4] (gait.py:16-22)
-        sd.period = gs[0];
-        sd.ih0 = iteration[b];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-          sd.off[l] = gs[1 + l];
-          sd.dur[l] = gs[5 + l];
-        }
-      }
-    }
-    st[PL_X] = xd;
-    st[PL_Y] = yd;
-    st[PL_YAW] = yawd;
-    st[PL_ROLL] = roll_init;
-    st[PL_PITCH] = pitch_init;
-    if (pp.integrate) st[PL_STARTED] = 1.0;
+  for (int k = 0; k < 3; ++k) {
+    xs[3 + k] = p3[k];
+    xs[6 + k] = w3[k];
+    xs[9 + k] = v3[k];
   }
-  if (!pp.mpc_tick) return;   // uniform over the workgroup
+  xs[12] = (float)(-pp.gravity);
+#pragma unroll
+  for (int k = 0; k < NX; ++k) x0[(size_t)b * NX + k] = xs[k];
+
+  // ---- desired velocity in the world frame: R_base @ v_body (mpc.py:83).  Without
+  // a caller-supplied R_base it is quat2matrix(quat) (robot_data.py:75,
+  // kinematics.py:51-71) in the same float32 scalar arithmetic
+  float R[9];
+  if (rot != nullptr) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = rot[9 * b + k];
+  } else {
+    plan_quat2matrix(qw, qx, qy, qz, R);
+  }
+  // the body-frame command is float64 (a Python list / float64 array in the scripts)
+  double vdes[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    vdes[r] = (double)R[3 * r] * vbody[3 * b] + (double)R[3 * r + 1] * vbody[3 * b + 1] +
+              (double)R[3 * r + 2] * vbody[3 * b + 2];
+  const double rate = yaw_rate[b];
+
+  // ---- pose integrators (mpc.py:84-92); the yaw is self.yaw = rpy[2] in float64
+  double* st = state + (size_t)b * 8;
+  const bool started = st[PL_STARTED] != 0.0;
+  double xd, yd, yawd;
+  if (pp.integrate) {
+    xd = started ? st[PL_X] + pp.dt_control * vdes[0] : 0.0;
+    yd = started ? st[PL_Y] + pp.dt_control * vdes[1] : 0.0;
+    yawd = started ? yaw + pp.dt_control * rate : yaw;
+  } else {   // generate_reference_trajectory alone (mpc.py:110) reads the last integration
+    xd = st[PL_X];
+    yd = st[PL_Y];
+    yawd = started ? st[PL_YAW] : yaw;
+  }
+  double roll_init = started ? st[PL_ROLL] : 0.0;
+  double pitch_init = started ? st[PL_PITCH] : 0.0;
+
+  if (pp.mpc_tick) {
+    // ---- position clamp (mpc.py:121-140)
+    const double px = xs[3], py = xs[4], e = pp.max_pos_error;
+    if (xd - px > e) xd = px + e;
+    if (px - xd > e) xd = px - e;
+    if (yd - py > e) yd = py + e;
+    if (py - yd > e) yd = py - e;
+    // ---- roll / pitch compensation (mpc.py:143-152), NumPy 1.x promotion: float64
+    const double vx = xs[9], vy = xs[10];
+    if (fabs(vx) > 0.2) pitch_init += pp.dt * (0.0 - (double)xs[1]) / vx;
+    if (fabs(vy) > 0.1) roll_init += pp.dt * (0.0 - (double)xs[0]) / vy;
+    roll_init = fmin(fmax(roll_init, -0.25), 0.25);
+    pitch_init = fmin(fmax(pitch_init, -0.25), 0.25);
+    sd.rate = rate;
+    sd.vx = vdes[0];
+    sd.vy = vdes[1];
+    sd.yawd = yawd;
+    sd.xd = xd;
+    sd.yd = yd;
+    sd.roll_comp = (float)(vy * roll_init);
+    sd.pitch_comp = (float)(vx * pitch_init);
+    sd.height = height[b];
+    if (gait != nullptr) {
+      const int* gs = gait + 9 * b;   // period, offsets[4], durations[4] (gait.py:16-22)
+      sd.period = gs[0];
+      sd.ih0 = iteration != nullptr ? iteration[b] : ih0;
+#pragma unroll
+      for (int l = 0; l < 4; ++l) {
+        sd.off[l] = gs[1 + l];
+        sd.dur[l] = gs[5 + l];
+      }
+    }
+  }
+  st[PL_X] = xd;
+  st[PL_Y] = yd;
+  st[PL_YAW] = yawd;
+  st[PL_ROLL] = roll_init;
+  st[PL_PITCH] = pitch_init;
+  if (pp.integrate) st[PL_STARTED] = 1.0;
+}
+
+// Phase 2 for the workgroup's `nrob` robots from b0 on, by all kPlanThreads threads `t` (every
+// one of them calls it: it holds two barriers).  seed_at(r) is robot r's PlanSeed in LDS, `seq`
+// the workgroup's [kPlanRobots][3][kMaxN] floats.
+template <class SeedAt>
+__device__ inline void plan_rows(const PlanParams& pp, int b0, int nrob, int t, SeedAt seed_at,
+                                 float (*seq)[3][kMaxN], const int* __restrict__ gait, float* __restrict__ xref,
+                                 float* __restrict__ contact) {
+#pragma clang fp contract(off)
+  const int N = pp.N;
   __syncthreads();
 
   // ---- yaw / x / y along the horizon (mpc.py:165-168) accumulate in float32
@@ -208,7 +191,7 @@ __global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
   // (robot, component), into LDS
   if (t < 3 * nrob) {
     const int r = t / 3, c = t - 3 * (t / 3);
-    const PlanSeed& sd = seed[r];
+    const PlanSeed& sd = seed_at(r);
     const double step = pp.dt * (c == 0 ? sd.rate : (c == 1 ? sd.vx : sd.vy));
     float a = (float)(c == 0 ? sd.yawd : (c == 1 ? sd.xd : sd.yd));
     float* q = seq[r][c];
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
   const int rows = nrob * N;
   for (int row = t; row < rows; row += kPlanThreads) {
     const int r = row / N, i = row - r * N;
-    const PlanSeed& sd = seed[r];
+    const PlanSeed& sd = seed_at(r);
     float* xr = xref + ((size_t)b0 * N + row) * NX;
     xr[0] = sd.roll_comp;
     xr[1] = sd.pitch_comp;
@@ -258,6 +241,48 @@ __global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
     }
     *reinterpret_cast<float4*>(contact + ((size_t)b0 * N + row) * 4) = make_float4(c[0], c[1], c[2], c[3]);
   }
+}
+
+__global__ __launch_bounds__(kPlanThreads) void mpcqp_plan_kernel(
+    PlanParams pp, int B, const float* __restrict__ quat, const float* __restrict__ pos,
+    const float* __restrict__ omega, const float* __restrict__ vel, const float* __restrict__ rot,
+    const double* __restrict__ vbody, const double* __restrict__ yaw_rate, const int* __restrict__ gait,
+    const int* __restrict__ iteration, const float* __restrict__ height, double* __restrict__ state,
+    float* __restrict__ x0, float* __restrict__ xref, float* __restrict__ contact) {
+  __shared__ PlanSeed seed[kPlanRobots];
+  __shared__ float seq[kPlanRobots][3][kMaxN];   // yaw / x / y along the horizon
+  const int b0 = blockIdx.x * kPlanRobots;
+  const int nrob = min(kPlanRobots, B - b0);
+  const int t = threadIdx.x;
+
+  if (t < nrob) {
+    const int b = b0 + t;
+    // ---- inputs: separate arrays, or one Isaac Gym actor-root-state row
+    // [pos(3), quat(x, y, z, w), lin_vel(3), ang_vel(3)] (isaacgym_a1.py:119-128)
+    float qw, qx, qy, qz, p3[3], w3[3], v3[3];
+    if (pp.root_layout) {
+      const float* rs = quat + (size_t)b * 13;
+      qx = rs[3], qy = rs[4], qz = rs[5], qw = rs[6];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        p3[k] = rs[k];
+        v3[k] = rs[7 + k];
+        w3[k] = rs[10 + k];
+      }
+    } else {
+      qw = quat[4 * b], qx = quat[4 * b + 1], qy = quat[4 * b + 2], qz = quat[4 * b + 3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        p3[k] = pos[3 * b + k];
+        w3[k] = omega[3 * b + k];
+        v3[k] = vel[3 * b + k];
+      }
+    }
+    plan_robot(pp, b, qw, qx, qy, qz, p3, w3, v3, rot, vbody, yaw_rate, gait, iteration, 0, height, state, x0,
+               seed[t]);
+  }
+  if (!pp.mpc_tick) return;   // uniform over the workgroup
+  plan_rows(pp, b0, nrob, t, [&](int r) -> const PlanSeed& { return seed[r]; }, seq, gait, xref, contact);
 }
 
 // tau_leg = Jv_leg^T (-f_leg) for legs in stance at the first horizon step

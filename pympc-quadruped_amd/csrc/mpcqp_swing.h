@@ -39,6 +39,64 @@ struct SwingBase {
   int period, off[4], dur[4], tick;
 };
 
+// One leg's control law on a lane (one text for mpcqp_leg_torque_kernel and mpcqp_step_kernel):
+// the swing decision on the robot's tick, then the stance expression or the swing generator and
+// PD law.  The robot's shared values (R_base, pos, vel as float32; the command) come from LDS,
+// the leg's kinematics J, th, pf, fp, fv as the float32 values mpcqp_kinematics stores, f its
+// force of u0; Kp, Kd the gains (sp's, or a copy of them).  m2 is the leg's generator state as loaded, mp where a leg in swing stores it
+// back.  Returns the torques tq, the targets pt / vt (zero in stance) and the swing state *sv.
+__device__ inline void swing_leg_control(const SwingParams& sp, const double* Kp, const double* Kd, int tick, int period, int off, int dur, int dur0,
+                                         const float* R32, const float* pos, const float* vel, const double* vbody,
+                                         double yaw_rate, const float (&J)[9], const float (&f)[3],
+                                         const float (&th)[3], const float (&pf)[3], const float (&fp)[3],
+                                         const float (&fv)[3], const double2 (&m2)[SW_LEG_STRIDE / 2], double2* mp,
+                                         float (&tq)[3], float (&pt)[3], float (&vt)[3], double* sv) {
+#pragma clang fp contract(off)
+  const int st = swing_decide(tick, sp.ibm, period, off, dur, sv);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pt[k] = vt[k] = 0.f;
+  if (st == SWING_STANCE) {
+    // tau_leg = Jv^T (-f_leg) (leg_controller.py:86-89), as mpcqp_stance_torque_kernel
+#pragma unroll
+    for (int j = 0; j < 3; ++j) tq[j] = -(J[j] * f[0] + J[3 + j] * f[1] + J[6 + j] * f[2]);
+  } else {
+    double R[9], p3[3], v3[3], vb[3], thd[3], pfd[3], fpd[3], fvd[3], Jd[9], mem[SW_LEG_STRIDE];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      R[k] = (double)R32[k];
+      Jd[k] = (double)J[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      p3[k] = (double)pos[k];
+      v3[k] = (double)vel[k];
+      vb[k] = vbody[k];
+      thd[k] = (double)th[k];
+      pfd[k] = (double)pf[k];
+      fpd[k] = (double)fp[k];
+      fvd[k] = (double)fv[k];
+    }
+#pragma unroll
+    for (int k = 0; k < SW_LEG_STRIDE / 2; ++k) {
+      mem[2 * k] = m2[k].x;
+      mem[2 * k + 1] = m2[k].y;
+    }
+    double t_swing, t_stance, pb[3], vbase[3], tqd[3];
+    swing_times(sp.dt_control, sp.ibm, period, dur0, &t_swing, &t_stance);
+    swing_leg_step(mem, st == SWING_FINISHED, sp.dt_control, t_swing, t_stance, p3, v3, R, vb, yaw_rate, thd, pfd,
+                   sp.gravity, sp.vel_gain, sp.touchdown_z, sp.swing_height, pb, vbase);
+#pragma unroll
+    for (int k = 0; k < SW_LEG_STRIDE / 2; ++k) mp[k] = make_double2(mem[2 * k], mem[2 * k + 1]);
+    swing_pd(R, Kp, Kd, Jd, pb, vbase, fpd, fvd, tqd);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      tq[k] = (float)tqd[k];
+      pt[k] = (float)pb[k];
+      vt[k] = (float)vbase[k];
+    }
+  }
+}
+
 __global__ __launch_bounds__(kSwingThreads) void mpcqp_leg_torque_kernel(
     SwingParams sp, int B, const int* __restrict__ tick, const float* __restrict__ quat,
     const float* __restrict__ pos, const float* __restrict__ vel, const float* __restrict__ rot,
@@ -126,48 +184,9 @@ __global__ __launch_bounds__(kSwingThreads) void mpcqp_leg_torque_kernel(
 
   const SwingBase& sb = base[r];
   double sv;
-  const int st = swing_decide(sb.tick, sp.ibm, sb.period, sb.off[leg], sb.dur[leg], &sv);
-  float tq[3], pt[3] = {0.f, 0.f, 0.f}, vt[3] = {0.f, 0.f, 0.f};
-  if (st == SWING_STANCE) {
-    // tau_leg = Jv^T (-f_leg) (leg_controller.py:86-89), as mpcqp_stance_torque_kernel
-#pragma unroll
-    for (int j = 0; j < 3; ++j) tq[j] = -(J[j] * f[0] + J[3 + j] * f[1] + J[6 + j] * f[2]);
-  } else {
-    double R[9], p3[3], v3[3], vb[3], thd[3], pfd[3], fpd[3], fvd[3], Jd[9], mem[SW_LEG_STRIDE];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      R[k] = (double)sb.R[k];
-      Jd[k] = (double)J[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      p3[k] = (double)sb.pos[k];
-      v3[k] = (double)sb.vel[k];
-      vb[k] = sb.vb[k];
-      thd[k] = (double)th[k];
-      pfd[k] = (double)pf[k];
-      fpd[k] = (double)fp[k];
-      fvd[k] = (double)fv[k];
-    }
-#pragma unroll
-    for (int k = 0; k < SW_LEG_STRIDE / 2; ++k) {
-      mem[2 * k] = m2[k].x;
-      mem[2 * k + 1] = m2[k].y;
-    }
-    double t_swing, t_stance, pb[3], vbase[3], tqd[3];
-    swing_times(sp.dt_control, sp.ibm, sb.period, sb.dur[0], &t_swing, &t_stance);
-    swing_leg_step(mem, st == SWING_FINISHED, sp.dt_control, t_swing, t_stance, p3, v3, R, vb, sb.yr, thd, pfd,
-                   sp.gravity, sp.vel_gain, sp.touchdown_z, sp.swing_height, pb, vbase);
-#pragma unroll
-    for (int k = 0; k < SW_LEG_STRIDE / 2; ++k) mp[k] = make_double2(mem[2 * k], mem[2 * k + 1]);
-    swing_pd(R, sp.Kp, sp.Kd, Jd, pb, vbase, fpd, fvd, tqd);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      tq[k] = (float)tqd[k];
-      pt[k] = (float)pb[k];
-      vt[k] = (float)vbase[k];
-    }
-  }
+  float tq[3], pt[3], vt[3];
+  swing_leg_control(sp, sp.Kp, sp.Kd, sb.tick, sb.period, sb.off[leg], sb.dur[leg], sb.dur[0], sb.R, sb.pos, sb.vel, sb.vb, sb.yr,
+                    J, f, th, pf, fp, fv, m2, mp, tq, pt, vt, &sv);
 #pragma unroll
   for (int k = 0; k < 3; ++k) tau[bl * 3 + k] = tq[k];
   if (swing_state != nullptr) swing_state[bl] = (float)sv;

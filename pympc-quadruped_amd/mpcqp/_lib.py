@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "mpcqp_set_swing",
     "mpcqp_kinematics",
     "mpcqp_kinematics_root_states",
+    "mpcqp_step",
     "mpcqp_estimate",
     "mpcqp_set_estimator",
     "mpcqp_attitude",
@@ -59,6 +60,7 @@ PLAN_REFERENCE = 1      # MPCQP_PLAN_REFERENCE: build X_ref (+ gait table) this 
 PLAN_NO_INTEGRATE = 2   # MPCQP_PLAN_NO_INTEGRATE: skip the desired-pose integrators
 SWING_STRIDE = 32   # MPCQP_SWING_STRIDE: float64 swing-generator state per robot (8 per leg)
 KIN_STRIDE = 8      # MPCQP_KIN_STRIDE: float64 leg geometry per robot (5 used)
+STEP_MPC = 1        # MPCQP_STEP_MPC: this tick solves (plan with the reference, solve, leg torques)
 EST_STRIDE = 352    # MPCQP_EST_STRIDE: float64 estimator record per robot (x[18], initialised, P at 24)
 EST_DOF_STATES = 1  # MPCQP_EST_DOF_STATES: q is a dof-state tensor [B,12,2], qdot ignored
 ATT_STRIDE = 8      # MPCQP_ATT_STRIDE: float64 orientation record per robot (q[4], initialised, gyro bias[3])
@@ -132,6 +134,8 @@ def load():
     lib.mpcqp_kinematics.argtypes = [vp, i32, i32] + [vp] * 14 + [vp]
     lib.mpcqp_kinematics_root_states.restype = ctypes.c_int
     lib.mpcqp_kinematics_root_states.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
+    lib.mpcqp_step.restype = ctypes.c_int
+    lib.mpcqp_step.argtypes = [vp, i32, i32, i32, vp, i32] + [vp] * 26 + [vp]
     lib.mpcqp_estimate.restype = ctypes.c_int
     lib.mpcqp_estimate.argtypes = [vp, i32, i32] + [vp] * 11 + [vp]
     lib.mpcqp_set_estimator.restype = ctypes.c_int

@@ -21,13 +21,15 @@ The per-robot Python loop it replaces is scripts/isaacgym_a1.py:117-162 (which
 copies every robot's root state to the host, ``.cpu().numpy()``); ``tick`` and
 ``leg_torques`` take the simulator's root-state tensor as it lies on the device
 (SURVEY §8 f3).  ``step`` is the whole loop body on the simulator's two state tensors,
-with nothing computed by the caller; ``tick`` and ``leg_torques`` remain for callers with
-kinematics of their own, ``torques`` for callers that run their own swing controller.
+with nothing computed by the caller; ``step_fused`` is the same tick, bit for bit, through
+one C call (mpcqp_step: one launch on a tick between two solves).  ``tick`` and
+``leg_torques`` remain for callers with kinematics of their own, ``torques`` for callers that
+run their own swing controller.
 """
 import numpy as np
 import torch
 
-from ._lib import PLAN_REFERENCE, PLAN_STRIDE, SWING_STRIDE
+from ._lib import PLAN_REFERENCE, PLAN_STRIDE, STEP_MPC, SWING_STRIDE
 from .engine import LinearMpc
 from .params import (DT_MPC, LEG_GEOMETRY, Q_DIAG, R_DIAG, ROBOT_PRESETS, SWING_PRESETS, gait_record,
                      pack_leg_geometry)
@@ -244,3 +246,73 @@ class BatchedController:
         self.tick(iter_counter, vel_body_des, yaw_rate_des, self.feet, root_states=rs)
         return self.leg_torques(iter_counter, vel_body_des, yaw_rate_des, self.thighs, self.pos_feet,
                                 self.foot_pos_base, self.foot_vel_base, self.jac, root_states=rs)
+
+    def set_command(self, vel_body_des, yaw_rate_des):
+        """Store the command on the device once: ``step_fused`` then takes None for both and
+        uploads nothing per call.  Tensors that already are contiguous float64 device tensors
+        of shape [B,3] / [B] are kept as they are (writing into them changes the command)."""
+        self._command = (self._cmd_fused(vel_body_des, (self.B, 3)), self._cmd_fused(yaw_rate_des, (self.B,)))
+        return self._command
+
+    def _cmd_fused(self, v, shape):
+        if (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.device == self.device
+                and tuple(v.shape) == shape and v.is_contiguous()):
+            return v
+        return self._cmd(v, shape)
+
+    def step_fused(self, iter_counter, vel_body_des, yaw_rate_des, root_states, dof_states, outputs=False,
+                   mpc_tick=None):
+        """``step`` in one C call (mpcqp_step): one launch on a tick between two solves, and on
+        an MPC tick (``iter_counter % iterations_between_mpc == 0``) the plan with the
+        reference, the solve and the leg controller enqueued together; returns tau [B,12]
+        (device).  It leaves u0, x0, plan_state, swing_mem, status and iterations -- on an MPC
+        tick xref, contact and feet too -- bitwise as ``step`` does.
+
+        ``vel_body_des`` / ``yaw_rate_des``: contiguous float64 device tensors of shape [B,3] /
+        [B] go through with no copy, anything else is converted as for ``step``; None for both
+        uses what ``set_command`` stored.  ``iter_counter``: an int reaches the kernel as an
+        argument (no fill; ``self.tick_count`` is left alone); None uses ``self.tick_count``,
+        each robot's own counter kept by the caller, and ``mpc_tick`` then says whether this
+        tick solves (left at None too, the first robot's counter is read back to decide, which
+        waits for the device).  ``outputs=True`` also fills self.thighs, pos_feet, foot_pos_base,
+        foot_vel_base, jac, swing_state, pos_target and vel_target, and self.feet on every
+        tick; with False those attributes keep whatever an earlier call left (self.feet: the
+        last MPC tick's)."""
+        if self.geometry is None:
+            raise ValueError("no leg geometry: pass geometry= (params.LEG_GEOMETRY, leg_geometry_from_urdf)")
+        dev, B = self.device, self.B
+        rs, ds = [t if t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+                  else t.to(dev, torch.float32).contiguous() for t in (root_states, dof_states)]
+        if rs.shape != (B, 13) or ds.numel() != B * 24:
+            raise ValueError(f"expected root_states [{B},13] and dof_states [{B},12,2], got "
+                             f"{tuple(rs.shape)} and {tuple(ds.shape)}")
+        if vel_body_des is None and yaw_rate_des is None:
+            if getattr(self, "_command", None) is None:
+                raise ValueError("no command: pass vel_body_des and yaw_rate_des, or call set_command first")
+            vb, yr = self._command
+        else:
+            vb, yr = self._cmd_fused(vel_body_des, (B, 3)), self._cmd_fused(yaw_rate_des, (B,))
+        ibm = self.iterations_between_mpc
+        per_robot = iter_counter is None
+        it = 0 if per_robot else int(iter_counter)
+        if mpc_tick is None:
+            mpc_tick = (int(self.tick_count[0]) if per_robot and B else it) % ibm == 0
+        mpc_tick = bool(mpc_tick)
+        # the pointer tuple is built once per set of buffers (the simulator's tensors and a
+        # stored command keep their addresses from tick to tick)
+        key = (rs.data_ptr(), ds.data_ptr(), vb.data_ptr(), yr.data_ptr(), bool(outputs), per_robot, mpc_tick)
+        cache = self.__dict__.setdefault("_fused", {})
+        launch = cache.get(key)
+        if launch is None:
+            if len(cache) >= 8:
+                cache.clear()
+            opt = dict(thighs=self.thighs, pos_feet=self.pos_feet, foot_pos_base=self.foot_pos_base,
+                       foot_vel_base=self.foot_vel_base, jac=self.jac, swing_state=self.swing_state,
+                       pos_target=self.pos_target, vel_target=self.vel_target) if outputs else {}
+            launch = cache[key] = self.engine.bind_step(
+                rs, ds, self.geometry, vb, yr, self.gait, self.plan_state, self.swing_mem, self.x0, self.u0,
+                self.tau, tick=self.tick_count if per_robot else None, height_des=self.height, robot=self.robot,
+                xref=self.xref, contact=self.contact, feet=self.feet if mpc_tick or outputs else None,
+                status=self.status, iters=self.iterations, **opt)
+        launch(STEP_MPC if mpc_tick else 0, it, ibm, torch.cuda.current_stream(dev))
+        return self.tau

@@ -417,6 +417,53 @@ class LinearMpc:
         launch.buffers = keep
         return launch
 
+    def step(self, flags, iter_counter, iterations_between_mpc, root_states, dof_states, geom, vel_body_des,
+             yaw_rate_des, gait, plan_state, swing_mem, x0, u0, tau, tick=None, height_des=None, robot=None,
+             xref=None, contact=None, feet=None, status=None, iters=None, thighs=None, pos_feet=None,
+             foot_pos_base=None, foot_vel_base=None, jac=None, swing_state=None, pos_target=None,
+             vel_target=None, stream=None):
+        """One whole control iteration of every robot in one call (include/mpcqp.h mpcqp_step;
+        isaacgym_a1.py:117-162): with ``flags`` 0 one launch -- kinematics, state packing, pose
+        integration and all 12 joint torques, the kinematic arrays never leaving the registers
+        unless asked for; with STEP_MPC the plan with the reference, the solve and the leg
+        controller on the fresh u0, enqueued by one call.  Bitwise what ``kinematics``, ``plan``,
+        ``solve_raw`` and ``leg_torques`` give on the same buffers.
+
+        Every argument is a preallocated contiguous device tensor, as for those four:
+        root_states [B,13] and dof_states [B,12,2] (Isaac Gym layout).  ``tick`` [B] int32 is
+        each robot's counter; None gives every robot the scalar ``iter_counter``.  height_des,
+        robot, xref, contact and feet are needed with STEP_MPC only; the last eight are
+        optional outputs."""
+        self.bind_step(root_states, dof_states, geom, vel_body_des, yaw_rate_des, gait, plan_state, swing_mem, x0,
+                       u0, tau, tick=tick, height_des=height_des, robot=robot, xref=xref, contact=contact,
+                       feet=feet, status=status, iters=iters, thighs=thighs, pos_feet=pos_feet,
+                       foot_pos_base=foot_pos_base, foot_vel_base=foot_vel_base, jac=jac, swing_state=swing_state,
+                       pos_target=pos_target, vel_target=vel_target)(
+            flags, iter_counter, iterations_between_mpc,
+            stream if stream is not None else torch.cuda.current_stream(self.device))
+
+    def bind_step(self, root_states, dof_states, geom, vel_body_des, yaw_rate_des, gait, plan_state, swing_mem, x0,
+                  u0, tau, tick=None, height_des=None, robot=None, xref=None, contact=None, feet=None, status=None,
+                  iters=None, thighs=None, pos_feet=None, foot_pos_base=None, foot_vel_base=None, jac=None,
+                  swing_state=None, pos_target=None, vel_target=None):
+        """step() with its device pointers resolved once: returns ``launch(flags, iter_counter,
+        iterations_between_mpc, stream)`` (see bind_solve)."""
+        lib, ctx = self.lib, self._ctx
+        B = int(tau.shape[0])
+        keep = (root_states, dof_states, geom, vel_body_des, yaw_rate_des, gait, height_des, robot, plan_state,
+                swing_mem, x0, xref, contact, feet, u0, tau, status, iters, thighs, pos_feet, foot_pos_base,
+                foot_vel_base, jac, swing_state, pos_target, vel_target)
+        tk = _ptr(tick)
+        tail = tuple(_ptr(t) for t in keep)
+        fn = lib.mpcqp_step
+
+        def launch(flags, iter_counter, iterations_between_mpc, stream):
+            code = fn(ctx, B, flags, iter_counter, tk, iterations_between_mpc, *tail, stream.cuda_stream)
+            if code:
+                _lib.check(ctx, code, "mpcqp_step")
+        launch.buffers = keep + (tick,)
+        return launch
+
     def set_estimator(self, dt=0.001, gravity=9.81, sigma_p=0.001, sigma_v=0.0098, sigma_f=0.002, r_p=0.001,
                       r_v=0.1, r_z=0.001, suspicion=100.0, p0=100.0, contact_height=0.0):
         """Estimator constants (include/mpcqp.h mpcqp_set_estimator; doc/state_estimation_kf.md):
