@@ -68,6 +68,7 @@ extern "C" {
 
 #define MPCQP_ABI_VERSION 6
 #define MPCQP_ROBOT_STRIDE 16
+#define MPCQP_ROBOT_NORMAL 9   /* first of the three words of the surface normal in a robot record */
 #define MPCQP_MAX_HORIZON 32   /* mpcqp_create rejects horizon > 32 (MPCQP_ERR_ARG).  Horizons
                                   up to 20 use every capacity class; longer ones are solved by
                                   the interior-point class alone (its per-robot LDS scratch is
@@ -555,6 +556,85 @@ int mpcqp_attitude(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* gy
  * [0, 0.5] returns MPCQP_ERR_ARG and leaves the previous constants in force. */
 int mpcqp_set_attitude(mpcqp_ctx* ctx, double dt, double gravity, double kappa_ref, double bias_gain,
                        double trust_window, double touch_threshold);
+
+/* ---- the terrain plane on the device: fit from the stance feet, cones and footholds ----
+ *
+ * mpcqp_terrain fits, for B robots in one launch, each robot's ground plane to the world
+ * positions its four feet had while last in contact: RobotData.update_terrain_normal
+ * (utils/robot_data.py:186-228), which the reference defines and never calls.  It produces the
+ * surface normal that the cone rows of mpcqp_solve read from words 9..11 of the robot record,
+ * and the plane that mpcqp_set_ground hands to the swing leg.  One thread per robot, one
+ * launch, no atomics, allocation, synchronisation or host read: it can be captured into a HIP
+ * graph (the record lives in caller memory, so a replay advances it).  Float64 arithmetic on
+ * the float32 inputs, each float32 output rounded once.
+ *
+ *   flags          MPCQP_TERRAIN_SWING_STATE: `contact` is the swing_state of mpcqp_leg_torques /
+ *                  mpcqp_step, and a foot is in contact where !(swing_state > 0), the leg
+ *                  controller's own rule for stance.  Without it a foot is in contact where
+ *                  contact > contact_threshold (a NaN is no contact).
+ *                  MPCQP_TERRAIN_ROOT_STATES: `quat` is an Isaac Gym root-state tensor [B][13];
+ *                  without it [B][4] as (w, x, y, z)
+ *   pos_feet       [B][4][3]  the feet in the world frame (mpcqp_kinematics' pos_feet,
+ *                             mpcqp_estimate's feet_world)
+ *   contact        [B][4]
+ *   quat           nullable; read for normal_base alone
+ *   terrain_state  [B][MPCQP_TERRAIN_STRIDE] float64 in/out, 16-byte aligned: history[4][3] at 0,
+ *                  initialised (0 / 1) at 12, n[3] at 13, d at 16, fitted (0 / 1) at 17, two
+ *                  zero words.  An all-zero record is "not initialised".
+ *   robot          nullable, in/out [B][MPCQP_ROBOT_STRIDE]: words 9..11 are written with
+ *                  `normal`, no other word is touched
+ * Outputs, each nullable (a NULL output is not written):
+ *   normal         [B][3]  n, unit length, n_z > 0
+ *   plane          [B][4]  n, d: the plane n . p = d through the centroid of the history
+ *   normal_base    [B][3]  R_base^T n (terrain_normal_est_yaw_aligned, :227), R_base the float32
+ *                          quat2matrix of mpcqp_plan; needs quat
+ *   status         [B]     MPCQP_STATUS_OK, or MPCQP_STATUS_NONFINITE for a robot with a
+ *                          non-finite foot among those it would latch, or a non-finite word in
+ *                          an initialised record: its record is not written and its outputs are
+ *                          formed from the record as it was ((0, 0, 1) and d = 0 if not
+ *                          initialised); no other robot is affected.  A non-finite foot that
+ *                          is not latched is ignored.
+ * One tick, with c_i the contact decision of foot i:
+ *   latch   a record not initialised takes all four feet, whatever c_i says, and n = (0, 0, 1);
+ *           an initialised one takes foot i where c_i holds
+ *   fit     mu = the mean of the history, S = sum_i (h_i - mu)(h_i - mu)^T; l0 <= l1 <= l2 its
+ *           eigenvalues and n_fit the eigenvector of l0 (6 cyclic Jacobi sweeps), flipped to
+ *           n_z >= 0
+ *   accept  l2 > 0, l1 - l0 > flat_tol l2 (the points span a plane: they are not collinear or
+ *           coincident) and n_fit_z >= cos_max_tilt:
+ *           n <- normalise((1 - blend) n + blend n_fit), fitted = 1; otherwise n stays, fitted = 0
+ *   d = n . mu either way
+ * Two deviations from the reference, which takes a row of numpy's eigenvector matrix where the
+ * eigenvector is the column, and whose seeding of the history is a no-op comparison so that it
+ * starts from four zero points: this is the column, and the first tick seeds all four feet.
+ * cos_max_tilt > 0 also keeps the normal off world +-x, where the solve's cone rows have no
+ * tangent frame.
+ *
+ * An unknown flag, batch < 0, a NULL pos_feet, contact or terrain_state, a misaligned
+ * terrain_state or normal_base without quat return MPCQP_ERR_ARG; batch == 0 is MPCQP_OK. */
+#define MPCQP_TERRAIN_STRIDE 20      /* doubles per robot */
+#define MPCQP_TERRAIN_SWING_STATE 1
+#define MPCQP_TERRAIN_ROOT_STATES 2
+int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos_feet, const float* contact,
+                  const float* quat, double* terrain_state, float* robot, float* normal, float* plane,
+                  float* normal_base, int32_t* status, void* stream);
+
+/* Constants of mpcqp_terrain: the contact threshold (0.5), flat_tol (1e-3), the cosine of the
+ * steepest plane accepted (0.5) and the weight of a new fit in n (1: no filter, as the
+ * reference).  A non-finite value, flat_tol outside [0, 1), cos_max_tilt outside (0, 1] or
+ * blend outside (0, 1] returns MPCQP_ERR_ARG and leaves the previous constants in force. */
+int mpcqp_set_terrain(mpcqp_ctx* ctx, double contact_threshold, double flat_tol, double cos_max_tilt,
+                      double blend);
+
+/* The swing leg's ground: `plane` is a caller-owned device buffer [capacity][4] of (n, d), what
+ * mpcqp_terrain writes, read by every later mpcqp_leg_torques* and mpcqp_step launch; it must
+ * outlive them.  Robot b < capacity in swing places its foothold at
+ * z = touchdown_z + ground(x, y), ground(x, y) = (d - n_x x - n_y y) / n_z, and its swing apex
+ * at swing_height + (ground(lift-off) + ground(foothold)) / 2.  A plane that is non-finite or
+ * has n_z <= 0 counts as none, as does b >= capacity: that robot walks on the reference's flat
+ * ground, bitwise as with nothing registered.  Stance legs do not read it.  NULL or capacity 0
+ * disables; capacity < 0, or a NULL plane with capacity > 0, returns MPCQP_ERR_ARG. */
+int mpcqp_set_ground(mpcqp_ctx* ctx, const float* plane, int32_t capacity);
 
 int mpcqp_destroy(mpcqp_ctx* ctx);
 

@@ -354,6 +354,7 @@ constexpr int kPrioTab = 4096;
 #include "mpcqp_step.h"
 #include "mpcqp_estimator.h"
 #include "mpcqp_attitude.h"
+#include "mpcqp_terrain.h"
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 
 // Workgroups are dealt round-robin over the 8 XCDs (block bid runs on XCD bid % 8,
@@ -703,6 +704,9 @@ struct mpcqp_ctx {
   double kd_swing[9];
   EstParams est;      // estimator constants (mpcqp_set_estimator)
   AttParams att;      // orientation-filter and contact-trust constants (mpcqp_set_attitude)
+  TerParams ter;      // terrain-plane constants (mpcqp_set_terrain)
+  const float* ground;   // the swing leg's ground planes (caller-owned device buffer), mpcqp_set_ground
+  int ground_cap;
   std::string err;
 };
 
@@ -866,6 +870,11 @@ int mpcqp_create(const mpcqp_params* p, int32_t device, mpcqp_ctx** out) {
   // the orientation filter: the document's kappa_ref, no bias estimate; the trust ramps over
   // the first and last fifth of the stance
   ctx->att = AttParams{0.001, 9.81, 0.1, 0.0, 0.2, 0.0};
+  // the terrain plane: a contact flag of 1 counts, the fit unfiltered as in the reference, held
+  // where the feet are nearly collinear or the plane steeper than 60 degrees
+  ctx->ter = TerParams{0.5, 1e-3, 0.5, 1.0, 0};
+  ctx->ground = nullptr;
+  ctx->ground_cap = 0;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->ncu = prop.multiProcessorCount;
   if (ctx->ncu <= 0) ctx->ncu = 256;
@@ -1303,6 +1312,8 @@ static int launch_leg_torques(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int 
   sp.vel_gain = ctx->vel_gain;
   memcpy(sp.Kp, ctx->kp_swing, sizeof(sp.Kp));
   memcpy(sp.Kd, ctx->kd_swing, sizeof(sp.Kd));
+  sp.ground = ctx->ground;
+  sp.ground_cap = ctx->ground_cap;
   hipLaunchKernelGGL(mpcqp_leg_torque_kernel, dim3((batch + kSwingRobots - 1) / kSwingRobots), dim3(kSwingThreads),
                      0, (hipStream_t)stream, sp, (int)batch, tick, quat, pos, vel, rot, vel_body_des, yaw_rate_des,
                      gait, thighs, pos_feet, foot_pos_base, foot_vel_base, jac, u0, swing_mem, tau, swing_state,
@@ -1412,6 +1423,8 @@ int mpcqp_step(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t iter_counte
   sp.sw.vel_gain = ctx->vel_gain;
   memcpy(sp.sw.Kp, ctx->kp_swing, sizeof(sp.sw.Kp));
   memcpy(sp.sw.Kd, ctx->kd_swing, sizeof(sp.sw.Kd));
+  sp.sw.ground = ctx->ground;
+  sp.sw.ground_cap = ctx->ground_cap;
   const dim3 grid((batch + kStepRobots - 1) / kStepRobots), block(kStepThreads);
   hipStream_t st = (hipStream_t)stream;
   auto launch = [&](auto kern, const char* what) -> int {
@@ -1512,6 +1525,60 @@ int mpcqp_attitude(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* gy
                      touch, att_state, quat, gyro_out, trust, status);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("attitude launch: ") + hipGetErrorString(e));
+  return MPCQP_OK;
+}
+
+// ---- the terrain plane (mpcqp_terrain.h): RobotData.update_terrain_normal (robot_data.py:186-228)
+// for every robot, producing the surface normal of the cone rows and the swing leg's ground plane.
+// An invalid constant leaves the previous set in force.
+int mpcqp_set_terrain(mpcqp_ctx* ctx, double contact_threshold, double flat_tol, double cos_max_tilt, double blend) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  const double all[4] = {contact_threshold, flat_tol, cos_max_tilt, blend};
+  for (double v : all)
+    if (!std::isfinite(v)) return set_err(ctx, MPCQP_ERR_ARG, "non-finite terrain constant");
+  if (flat_tol < 0.0 || !(flat_tol < 1.0)) return set_err(ctx, MPCQP_ERR_ARG, "terrain: flat_tol outside [0, 1)");
+  if (!(cos_max_tilt > 0.0) || cos_max_tilt > 1.0)
+    return set_err(ctx, MPCQP_ERR_ARG, "terrain: cos_max_tilt outside (0, 1]");
+  if (!(blend > 0.0) || blend > 1.0) return set_err(ctx, MPCQP_ERR_ARG, "terrain: blend outside (0, 1]");
+  ctx->ter = TerParams{contact_threshold, flat_tol, cos_max_tilt, blend, 0};
+  return MPCQP_OK;
+}
+
+int mpcqp_set_ground(mpcqp_ctx* ctx, const float* plane, int32_t capacity) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (capacity < 0 || (capacity > 0 && !plane))
+    return set_err(ctx, MPCQP_ERR_ARG, "ground: capacity < 0, or no plane for capacity > 0");
+  ctx->ground = capacity > 0 ? plane : nullptr;
+  ctx->ground_cap = capacity > 0 ? capacity : 0;
+  return MPCQP_OK;
+}
+
+int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos_feet, const float* contact,
+                  const float* quat, double* terrain_state, float* robot, float* normal, float* plane,
+                  float* normal_base, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (flags & ~(MPCQP_TERRAIN_SWING_STATE | MPCQP_TERRAIN_ROOT_STATES))
+    return set_err(ctx, MPCQP_ERR_ARG, "unknown terrain flags");
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "terrain: batch < 0");
+  if (!pos_feet || !contact || !terrain_state)
+    return set_err(ctx, MPCQP_ERR_ARG, "null terrain input/state pointer");
+  if ((uintptr_t)terrain_state & 15) return set_err(ctx, MPCQP_ERR_ARG, "terrain_state is not 16-byte aligned");
+  if (normal_base && !quat) return set_err(ctx, MPCQP_ERR_ARG, "terrain: normal_base wanted without quat");
+  if (batch == 0) return MPCQP_OK;
+  static_assert(TER_STRIDE == MPCQP_TERRAIN_STRIDE, "record stride");
+  static_assert(TER_ROBOT_STRIDE == MPCQP_ROBOT_STRIDE && TER_ROBOT_NORMAL == MPCQP_ROBOT_NORMAL &&
+                    MPCQP_ROBOT_NORMAL + 3 <= MPCQP_ROBOT_STRIDE, "the normal's words of the robot record");
+  static_assert(TER_SWING_STATE == MPCQP_TERRAIN_SWING_STATE && TER_ROOT_STATES == MPCQP_TERRAIN_ROOT_STATES, "flags");
+  static_assert(TER_STATUS_OK == MPCQP_STATUS_OK && TER_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  TerParams tp = ctx->ter;
+  tp.flags = flags;
+  hipLaunchKernelGGL(mpcqp_terrain_kernel, dim3((batch + kTerThreads - 1) / kTerThreads), dim3(kTerThreads), 0,
+                     (hipStream_t)stream, tp, (int)batch, pos_feet, contact, quat, terrain_state, robot, normal, plane,
+                     normal_base, status);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("terrain launch: ") + hipGetErrorString(e));
   return MPCQP_OK;
 }
 

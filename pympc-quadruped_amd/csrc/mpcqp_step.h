@@ -40,6 +40,7 @@ struct StepBase {
   double Rq[9], geom[5], vb[3], yr;
   PlanSeed seed;   // STEP_FRONT: the row seeds of plan_rows
   float pos[3], vel[3], omega[3], R[9];
+  float ground[4];   // swing_load_ground
   int period, off[4], dur[4], tick;
 };
 static_assert(sizeof(StepBase) * kStepRobots + sizeof(float) * kStepRobots * 3 * kMaxN < 64 * 1024,
@@ -126,6 +127,8 @@ __device__ inline void step_load(const StepParams& sp, int b, int leg, StepBase&
       sb.dur[l] = gs[5 + l];
     }
     sb.tick = tick != nullptr ? tick[b] : iter_counter;
+  } else if (MODE != STEP_FRONT) {
+    swing_load_ground(sp.sw, b, sb.ground);
   }
 }
 
@@ -242,8 +245,8 @@ __global__ __launch_bounds__(kStepThreads) void mpcqp_step_kernel(
     const StepBase& sb = base[r];
     double sv;
     float tq[3], pt[3], vt[3];
-    swing_leg_control(sp.sw, gains, gains + 9, sb.tick, sb.period, sb.off[leg], sb.dur[leg], sb.dur[0], sb.R, sb.pos, sb.vel, sb.vb,
-                      sb.yr, J, f, th, pf, fp, fv, m2, mp, tq, pt, vt, &sv);
+    swing_leg_control(sp.sw, gains, gains + 9, sb.tick, sb.period, sb.off[leg], sb.dur[leg], sb.dur[0], sb.R, sb.pos, sb.vel, sb.ground,
+                      sb.vb, sb.yr, J, f, th, pf, fp, fv, m2, mp, tq, pt, vt, &sv);
     step_store3(tau, bl, tq);
     if (swing_state != nullptr) swing_state[bl] = (float)sv;
     step_store3(pos_target, bl, pt);

@@ -23,6 +23,8 @@ struct SwingParams {
   double touchdown_z;
   double vel_gain;
   double Kp[9], Kd[9];
+  const float* ground;   // mpcqp_set_ground: [ground_cap][4] planes (n, d), or NULL
+  int ground_cap;
 };
 
 // A workgroup owns kSwingRobots consecutive robots, one thread per (robot, leg) with a
@@ -36,18 +38,27 @@ constexpr int kSwingThreads = 256;
 struct SwingBase {
   double vb[3], yr;
   float pos[3], vel[3], R[9];
+  float ground[4];   // swing_load_ground
   int period, off[4], dur[4], tick;
 };
 
+// Robot b's ground plane into its LDS record, read once per robot (on the lane of leg 3, which
+// fetches nothing else); zeros -- no plane -- with none registered or for a robot past the capacity
+__device__ inline void swing_load_ground(const SwingParams& sp, int b, float* g) {
+  const bool on = sp.ground != nullptr && b < sp.ground_cap;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g[k] = on ? sp.ground[4 * (size_t)b + k] : 0.f;
+}
+
 // One leg's control law on a lane (one text for mpcqp_leg_torque_kernel and mpcqp_step_kernel):
 // the swing decision on the robot's tick, then the stance expression or the swing generator and
-// PD law.  The robot's shared values (R_base, pos, vel as float32; the command) come from LDS,
+// PD law.  The robot's shared values (R_base, pos, vel, the ground plane g32 as float32; the command) come from LDS,
 // the leg's kinematics J, th, pf, fp, fv as the float32 values mpcqp_kinematics stores, f its
 // force of u0; Kp, Kd the gains (sp's, or a copy of them).  m2 is the leg's generator state as loaded, mp where a leg in swing stores it
 // back.  Returns the torques tq, the targets pt / vt (zero in stance) and the swing state *sv.
 __device__ inline void swing_leg_control(const SwingParams& sp, const double* Kp, const double* Kd, int tick, int period, int off, int dur, int dur0,
-                                         const float* R32, const float* pos, const float* vel, const double* vbody,
-                                         double yaw_rate, const float (&J)[9], const float (&f)[3],
+                                         const float* R32, const float* pos, const float* vel, const float* g32,
+                                         const double* vbody, double yaw_rate, const float (&J)[9], const float (&f)[3],
                                          const float (&th)[3], const float (&pf)[3], const float (&fp)[3],
                                          const float (&fv)[3], const double2 (&m2)[SW_LEG_STRIDE / 2], double2* mp,
                                          float (&tq)[3], float (&pt)[3], float (&vt)[3], double* sv) {
@@ -82,9 +93,10 @@ __device__ inline void swing_leg_control(const SwingParams& sp, const double* Kp
       mem[2 * k + 1] = m2[k].y;
     }
     double t_swing, t_stance, pb[3], vbase[3], tqd[3];
+    const double gd[4] = {(double)g32[0], (double)g32[1], (double)g32[2], (double)g32[3]};
     swing_times(sp.dt_control, sp.ibm, period, dur0, &t_swing, &t_stance);
-    swing_leg_step(mem, st == SWING_FINISHED, sp.dt_control, t_swing, t_stance, p3, v3, R, vb, yaw_rate, thd, pfd,
-                   sp.gravity, sp.vel_gain, sp.touchdown_z, sp.swing_height, pb, vbase);
+    swing_leg_step_ground(mem, st == SWING_FINISHED, sp.dt_control, t_swing, t_stance, p3, v3, R, vb, yaw_rate, thd,
+                          pfd, sp.gravity, sp.vel_gain, sp.touchdown_z, sp.swing_height, pb, vbase, gd);
 #pragma unroll
     for (int k = 0; k < SW_LEG_STRIDE / 2; ++k) mp[k] = make_double2(mem[2 * k], mem[2 * k + 1]);
     swing_pd(R, Kp, Kd, Jd, pb, vbase, fpd, fvd, tqd);
@@ -177,6 +189,8 @@ __global__ __launch_bounds__(kSwingThreads) void mpcqp_leg_torque_kernel(
         sb.dur[l] = gs[5 + l];
       }
       sb.tick = tick[b];
+    } else {
+      swing_load_ground(sp, b, sb.ground);
     }
   }
   __syncthreads();
@@ -185,8 +199,8 @@ __global__ __launch_bounds__(kSwingThreads) void mpcqp_leg_torque_kernel(
   const SwingBase& sb = base[r];
   double sv;
   float tq[3], pt[3], vt[3];
-  swing_leg_control(sp, sp.Kp, sp.Kd, sb.tick, sb.period, sb.off[leg], sb.dur[leg], sb.dur[0], sb.R, sb.pos, sb.vel, sb.vb, sb.yr,
-                    J, f, th, pf, fp, fv, m2, mp, tq, pt, vt, &sv);
+  swing_leg_control(sp, sp.Kp, sp.Kd, sb.tick, sb.period, sb.off[leg], sb.dur[leg], sb.dur[0], sb.R, sb.pos, sb.vel, sb.ground,
+                    sb.vb, sb.yr, J, f, th, pf, fp, fv, m2, mp, tq, pt, vt, &sv);
 #pragma unroll
   for (int k = 0; k < 3; ++k) tau[bl * 3 + k] = tq[k];
   if (swing_state != nullptr) swing_state[bl] = (float)sv;

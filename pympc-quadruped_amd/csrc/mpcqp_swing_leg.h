@@ -182,15 +182,25 @@ __host__ __device__ inline void swing_pd(const double* R, const double* Kp, cons
   swing_mat3t(J, e, tau);
 }
 
+// The ground's height at (x, y): z on the plane n . p = d, g = (n_x, n_y, n_z, d), n_z > 0
+__host__ __device__ inline double swing_ground(const double* g, double x, double y) {
+#pragma clang fp contract(off)
+  return ((g[3] - g[0] * x) - g[1] * y) / g[2];
+}
+
 // One tick of one leg's generator for a leg in swing (isaacgym_a1.py:150-160): advance
 // the foot-placement state machine in `mem` (SW_LEG_STRIDE doubles), then evaluate the
 // curve and change frame.  `foot_world` = pos_feet[leg], latched on the first swing tick.
-__host__ __device__ inline void swing_leg_step(double* mem, bool finished, double dt_control, double t_swing,
-                                               double t_stance, const double* pos, const double* vel, const double* R,
-                                               const double* vbody, double yaw_rate, const double* thigh,
-                                               const double* foot_world, double gravity, double vel_gain,
-                                               double touchdown_z, double swing_height, double* p_base,
-                                               double* v_base) {
+// `ground`: the robot's ground plane (n_x, n_y, n_z, d; mpcqp_set_ground), or NULL.  On a plane
+// the foothold's z is touchdown_z above the ground at the foothold, and the apex swing_height
+// above the mean of the ground at lift-off and at the foothold; a plane that is non-finite or
+// has n_z <= 0 counts as none, and without one both are the world z the reference uses.
+__host__ __device__ inline void swing_leg_step_ground(double* mem, bool finished, double dt_control, double t_swing,
+                                                      double t_stance, const double* pos, const double* vel,
+                                                      const double* R, const double* vbody, double yaw_rate,
+                                                      const double* thigh, const double* foot_world, double gravity,
+                                                      double vel_gain, double touchdown_z, double swing_height,
+                                                      double* p_base, double* v_base, const double* ground) {
 #pragma clang fp contract(off)
   const bool first = mem[SW_ARMED] == 0.0;
   const double remaining = first ? t_swing : mem[SW_REMAIN] - dt_control;
@@ -200,7 +210,26 @@ __host__ __device__ inline void swing_leg_step(double* mem, bool finished, doubl
   if (first)
     for (int k = 0; k < 3; ++k) mem[SW_INIT + k] = foot_world[k];
   mem[SW_ARMED] = finished ? 0.0 : 1.0;   // swing_state >= 1 re-arms the first-swing flag
+  double apex = swing_height;
+  if (ground != nullptr && isfinite(ground[0]) && isfinite(ground[1]) && isfinite(ground[2]) &&
+      isfinite(ground[3]) && ground[2] > 0.0) {
+    const double gf = swing_ground(ground, mem[SW_FINAL], mem[SW_FINAL + 1]);
+    const double gi = swing_ground(ground, mem[SW_INIT], mem[SW_INIT + 1]);
+    mem[SW_FINAL + 2] = touchdown_z + gf;
+    apex = swing_height + (gi + gf) / 2.0;
+  }
   double p[3], v[3];
-  swing_curve(t_swing, t_swing - remaining, mem + SW_INIT, mem + SW_FINAL, swing_height, p, v);
+  swing_curve(t_swing, t_swing - remaining, mem + SW_INIT, mem + SW_FINAL, apex, p, v);
   swing_to_base(R, pos, vel, p, v, p_base, v_base);
+}
+
+// the same on the flat ground of the reference
+__host__ __device__ inline void swing_leg_step(double* mem, bool finished, double dt_control, double t_swing,
+                                               double t_stance, const double* pos, const double* vel, const double* R,
+                                               const double* vbody, double yaw_rate, const double* thigh,
+                                               const double* foot_world, double gravity, double vel_gain,
+                                               double touchdown_z, double swing_height, double* p_base,
+                                               double* v_base) {
+  swing_leg_step_ground(mem, finished, dt_control, t_swing, t_stance, pos, vel, R, vbody, yaw_rate, thigh,
+                        foot_world, gravity, vel_gain, touchdown_z, swing_height, p_base, v_base, nullptr);
 }

@@ -51,6 +51,9 @@ EXPORTED_SYMBOLS = (
     "mpcqp_set_estimator",
     "mpcqp_attitude",
     "mpcqp_set_attitude",
+    "mpcqp_terrain",
+    "mpcqp_set_terrain",
+    "mpcqp_set_ground",
 )
 ABI_VERSION = 6
 WARM_BYTES = 128     # MPCQP_WARM_BYTES: warm-start memory per robot
@@ -64,6 +67,9 @@ STEP_MPC = 1        # MPCQP_STEP_MPC: this tick solves (plan with the reference,
 EST_STRIDE = 352    # MPCQP_EST_STRIDE: float64 estimator record per robot (x[18], initialised, P at 24)
 EST_DOF_STATES = 1  # MPCQP_EST_DOF_STATES: q is a dof-state tensor [B,12,2], qdot ignored
 ATT_STRIDE = 8      # MPCQP_ATT_STRIDE: float64 orientation record per robot (q[4], initialised, gyro bias[3])
+TERRAIN_STRIDE = 20        # MPCQP_TERRAIN_STRIDE: float64 terrain record per robot (history[4][3], initialised, n[3], d, fitted)
+TERRAIN_SWING_STATE = 1    # MPCQP_TERRAIN_SWING_STATE: contact is a swing_state, stance where !(value > 0)
+TERRAIN_ROOT_STATES = 2    # MPCQP_TERRAIN_ROOT_STATES: quat is a root-state tensor [B,13]
 
 
 class MpcqpParams(ctypes.Structure):
@@ -144,6 +150,12 @@ def load():
     lib.mpcqp_attitude.argtypes = [vp, i32, i32, vp, vp, vp, i32] + [vp] * 7 + [vp]
     lib.mpcqp_set_attitude.restype = ctypes.c_int
     lib.mpcqp_set_attitude.argtypes = [vp] + [ctypes.c_double] * 6
+    lib.mpcqp_terrain.restype = ctypes.c_int
+    lib.mpcqp_terrain.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
+    lib.mpcqp_set_terrain.restype = ctypes.c_int
+    lib.mpcqp_set_terrain.argtypes = [vp] + [ctypes.c_double] * 4
+    lib.mpcqp_set_ground.restype = ctypes.c_int
+    lib.mpcqp_set_ground.argtypes = [vp, vp, i32]
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise MpcqpError("libmpcqp ABI version mismatch")
     _lib = lib

@@ -535,3 +535,79 @@ class LinearMpc:
                                        _ptr(quat), _ptr(gyro_out), _ptr(trust), _ptr(status),
                                        ctypes.c_void_p(stream.cuda_stream))
         _lib.check(self._ctx, code, "mpcqp_attitude")
+
+    def set_terrain(self, contact_threshold=0.5, flat_tol=1e-3, cos_max_tilt=0.5, blend=1.0):
+        """Constants of ``terrain`` (include/mpcqp.h mpcqp_set_terrain): the contact threshold, the
+        tolerance below which the latched feet count as collinear ((l1 - l0) <= flat_tol l2, the
+        fit is held), the cosine of the steepest plane accepted and the weight of a new fit in
+        the normal (1: no filter, as the reference).  Like set_attitude, every call sets all of
+        them; an invalid value raises and keeps the previous constants."""
+        code = self.lib.mpcqp_set_terrain(self._ctx, float(contact_threshold), float(flat_tol), float(cos_max_tilt),
+                                          float(blend))
+        _lib.check(self._ctx, code, "mpcqp_set_terrain")
+        self.terrain_constants = dict(contact_threshold=contact_threshold, flat_tol=flat_tol,
+                                      cos_max_tilt=cos_max_tilt, blend=blend)
+
+    def set_ground(self, plane):
+        """The swing leg's ground (include/mpcqp.h mpcqp_set_ground): ``plane`` [capacity,4]
+        float32 on the device, (n, d) per robot as ``terrain`` writes it, read by every later
+        ``leg_torques`` and ``step`` launch; robot b < capacity places its foothold and its swing
+        apex on it.  None disables.  The engine keeps the tensor alive."""
+        if plane is None:
+            code = self.lib.mpcqp_set_ground(self._ctx, None, 0)
+        else:
+            if not (plane.dtype == torch.float32 and plane.is_contiguous() and plane.dim() == 2
+                    and plane.shape[1] == 4 and plane.device == self.device):
+                raise ValueError("set_ground: plane must be a contiguous float32 [capacity,4] tensor on the engine's device")
+            code = self.lib.mpcqp_set_ground(self._ctx, _ptr(plane), int(plane.shape[0]))
+        _lib.check(self._ctx, code, "mpcqp_set_ground")
+        self._ground = plane   # the context holds its pointer: keep it alive
+
+    def terrain(self, terrain_state, pos_feet, contact=None, swing_state=None, quat=None, root_states=None,
+                robot=None, normal=None, plane=None, normal_base=None, status=None, stream=None):
+        """One tick of every robot's terrain plane (include/mpcqp.h mpcqp_terrain): the feet in the
+        world frame and their contact state in, the ground plane fitted to the feet last in
+        contact out, in one launch on the current stream.
+
+        Every argument is a preallocated contiguous device tensor: terrain_state
+        [B,TERRAIN_STRIDE] float64, status [B] int32, the rest float32.  Inputs: pos_feet
+        [B,4,3]; contact [B,4] (in contact above the threshold) or ``swing_state`` [B,4] in its
+        place (in contact where not > 0); for normal_base, quat [B,4] (w, x, y, z) or
+        ``root_states`` [B,13].  ``robot`` [B,16]: its words 9..11, the cone rows' surface
+        normal, are overwritten.  Outputs, each optional: normal [B,3], plane [B,4] (n, d),
+        normal_base [B,3], status [B].  A tensor of another size, dtype or device, or one
+        that is not contiguous, raises ValueError: the kernel reads and writes B rows of each."""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        if (contact is None) == (swing_state is None):
+            raise ValueError("terrain: give contact or swing_state")
+        if quat is not None and root_states is not None:
+            raise ValueError("terrain: give quat or root_states, not both")
+        if terrain_state.dim() != 2 or terrain_state.shape[1] != _lib.TERRAIN_STRIDE:
+            raise ValueError(f"terrain: terrain_state must be [B,{_lib.TERRAIN_STRIDE}]")
+        B = int(terrain_state.shape[0])
+        f32, i32 = torch.float32, torch.int32
+        for name, t, shape, dtype in (
+                ("terrain_state", terrain_state, (B, _lib.TERRAIN_STRIDE), torch.float64),
+                ("pos_feet", pos_feet, (B, 4, 3), f32), ("contact", contact, (B, 4), f32),
+                ("swing_state", swing_state, (B, 4), f32), ("quat", quat, (B, 4), f32),
+                ("root_states", root_states, (B, 13), f32), ("robot", robot, (B, ROBOT_STRIDE), f32),
+                ("normal", normal, (B, 3), f32), ("plane", plane, (B, 4), f32),
+                ("normal_base", normal_base, (B, 3), f32), ("status", status, (B,), i32)):
+            if t is None:
+                if name == "pos_feet":
+                    raise ValueError("terrain: pos_feet is required")
+                continue
+            if not (t.dtype == dtype and t.is_contiguous() and t.device == self.device
+                    and t.numel() == int(np.prod(shape))):
+                raise ValueError(f"terrain: {name} must be a contiguous {dtype} tensor of shape {list(shape)} on "
+                                 f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        flags = 0
+        if swing_state is not None:
+            flags, contact = flags | _lib.TERRAIN_SWING_STATE, swing_state
+        if root_states is not None:
+            flags, quat = flags | _lib.TERRAIN_ROOT_STATES, root_states
+        code = self.lib.mpcqp_terrain(self._ctx, B, flags, _ptr(pos_feet), _ptr(contact), _ptr(quat),
+                                      _ptr(terrain_state), _ptr(robot), _ptr(normal), _ptr(plane),
+                                      _ptr(normal_base), _ptr(status), ctypes.c_void_p(stream.cuda_stream))
+        _lib.check(self._ctx, code, "mpcqp_terrain")
