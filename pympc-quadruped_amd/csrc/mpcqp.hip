@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <initializer_list>
 #include <string.h>
 
 #include <new>
@@ -355,7 +356,16 @@ constexpr int kPrioTab = 4096;
 #include "mpcqp_estimator.h"
 #include "mpcqp_attitude.h"
 #include "mpcqp_terrain.h"
+// the kernel headers' constants are those of include/mpcqp.h
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
+static_assert(EST_STRIDE == MPCQP_EST_STRIDE, "estimator record stride");
+static_assert(ATT_STRIDE == MPCQP_ATT_STRIDE, "attitude record stride");
+static_assert(ATT_STATUS_OK == MPCQP_STATUS_OK && ATT_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
+static_assert(TER_STRIDE == MPCQP_TERRAIN_STRIDE, "terrain record stride");
+static_assert(TER_ROBOT_STRIDE == MPCQP_ROBOT_STRIDE && TER_ROBOT_NORMAL == MPCQP_ROBOT_NORMAL &&
+                  MPCQP_ROBOT_NORMAL + 3 <= MPCQP_ROBOT_STRIDE, "the normal's words of the robot record");
+static_assert(TER_SWING_STATE == MPCQP_TERRAIN_SWING_STATE && TER_ROOT_STATES == MPCQP_TERRAIN_ROOT_STATES, "flags");
+static_assert(TER_STATUS_OK == MPCQP_STATUS_OK && TER_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
 
 // Workgroups are dealt round-robin over the 8 XCDs (block bid runs on XCD bid % 8,
 // MI355X_MICROARCH.md "Workgroup dispatch"; speed only, never correctness).  Block bid
@@ -713,6 +723,42 @@ struct mpcqp_ctx {
 static int set_err(mpcqp_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;
   return code;
+}
+
+// After a kernel launch: MPCQP_OK, or the launch error as "<what>: <HIP's text>".
+static int launched(mpcqp_ctx* ctx, const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return MPCQP_OK;
+  return set_err(ctx, MPCQP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// MPCQP_OK for a 16-byte aligned record buffer, else the refusal that names it.
+static int aligned16(mpcqp_ctx* ctx, const void* p, const char* name) {
+  if (((uintptr_t)p & 15) == 0) return MPCQP_OK;
+  return set_err(ctx, MPCQP_ERR_ARG, std::string(name) + " is not 16-byte aligned");
+}
+
+static bool all_finite(std::initializer_list<double> values) {
+  for (double v : values)
+    if (!std::isfinite(v)) return false;
+  return true;
+}
+
+// The swing-leg constants of a launch: every kernel that moves a swing leg takes them from here.
+static SwingParams swing_params(const mpcqp_ctx* ctx, int ibm, int root_layout) {
+  SwingParams sp;
+  sp.ibm = ibm;
+  sp.root_layout = root_layout;
+  sp.dt_control = ctx->dt_control;
+  sp.gravity = ctx->gravity;
+  sp.swing_height = ctx->swing_height;
+  sp.touchdown_z = ctx->touchdown_z;
+  sp.vel_gain = ctx->vel_gain;
+  memcpy(sp.Kp, ctx->kp_swing, sizeof(sp.Kp));
+  memcpy(sp.Kd, ctx->kd_swing, sizeof(sp.Kd));
+  sp.ground = ctx->ground;
+  sp.ground_cap = ctx->ground_cap;
+  return sp;
 }
 
 // Makes the context's device current for one ABI call and restores the caller's.
@@ -1189,7 +1235,7 @@ int mpcqp_set_weights(mpcqp_ctx* ctx, const double* Q, const double* R) {
 
 int mpcqp_set_planner(mpcqp_ctx* ctx, double dt_control, double gravity, double max_pos_error) {
   if (!ctx) return MPCQP_ERR_ARG;
-  if (!std::isfinite(dt_control) || !std::isfinite(gravity) || !std::isfinite(max_pos_error))
+  if (!all_finite({dt_control, gravity, max_pos_error}))
     return set_err(ctx, MPCQP_ERR_ARG, "non-finite planner constant");
   if (dt_control < 0.0 || max_pos_error < 0.0)
     return set_err(ctx, MPCQP_ERR_ARG, "negative planner constant (dt_control, max_pos_error)");
@@ -1231,9 +1277,7 @@ static int launch_plan(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int root_la
   hipLaunchKernelGGL(mpcqp_plan_kernel, dim3((batch + kPlanRobots - 1) / kPlanRobots), dim3(kPlanThreads), 0,
                      (hipStream_t)stream, pp, (int)batch, quat, pos, omega, vel, rot, vel_body_des, yaw_rate_des,
                      gait, iteration, height_des, plan_state, x0, xref, contact);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("plan launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched(ctx, "plan launch");
 }
 
 int mpcqp_plan(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* quat, const float* pos,
@@ -1264,15 +1308,13 @@ int mpcqp_stance_torques(mpcqp_ctx* ctx, int32_t batch, const float* jac, const 
   const int threads = (int)batch * 12;
   hipLaunchKernelGGL(mpcqp_stance_torque_kernel, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (int)batch, jac, contact, (int)contact_stride, u0, tau);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("torque launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched(ctx, "torque launch");
 }
 
 int mpcqp_set_swing(mpcqp_ctx* ctx, double swing_height, const double* Kp, const double* Kd, double touchdown_z,
                     double vel_gain) {
   if (!ctx) return MPCQP_ERR_ARG;
-  bool finite = std::isfinite(swing_height) && std::isfinite(touchdown_z) && std::isfinite(vel_gain);
+  bool finite = all_finite({swing_height, touchdown_z, vel_gain});
   for (int i = 0; i < 9 && finite; ++i)
     finite = (!Kp || std::isfinite(Kp[i])) && (!Kd || std::isfinite(Kd[i]));
   if (!finite) return set_err(ctx, MPCQP_ERR_ARG, "non-finite swing constant");
@@ -1299,29 +1341,15 @@ static int launch_leg_torques(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int 
   if (!tick || !quat || (!root_layout && (!pos || !vel)) || !vel_body_des || !yaw_rate_des || !gait || !thighs ||
       !pos_feet || !foot_pos_base || !foot_vel_base || !jac || !u0 || !swing_mem || !tau)
     return set_err(ctx, MPCQP_ERR_ARG, "null leg-torque input/output pointer");
-  if ((uintptr_t)swing_mem & 15) return set_err(ctx, MPCQP_ERR_ARG, "swing_mem is not 16-byte aligned");
+  if (int rc = aligned16(ctx, swing_mem, "swing_mem")) return rc;
   DeviceScope dev(ctx->device);
   if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
-  SwingParams sp;
-  sp.ibm = iterations_between_mpc;
-  sp.root_layout = root_layout;
-  sp.dt_control = ctx->dt_control;
-  sp.gravity = ctx->gravity;
-  sp.swing_height = ctx->swing_height;
-  sp.touchdown_z = ctx->touchdown_z;
-  sp.vel_gain = ctx->vel_gain;
-  memcpy(sp.Kp, ctx->kp_swing, sizeof(sp.Kp));
-  memcpy(sp.Kd, ctx->kd_swing, sizeof(sp.Kd));
-  sp.ground = ctx->ground;
-  sp.ground_cap = ctx->ground_cap;
+  const SwingParams sp = swing_params(ctx, iterations_between_mpc, root_layout);
   hipLaunchKernelGGL(mpcqp_leg_torque_kernel, dim3((batch + kSwingRobots - 1) / kSwingRobots), dim3(kSwingThreads),
                      0, (hipStream_t)stream, sp, (int)batch, tick, quat, pos, vel, rot, vel_body_des, yaw_rate_des,
                      gait, thighs, pos_feet, foot_pos_base, foot_vel_base, jac, u0, swing_mem, tau, swing_state,
                      pos_target, vel_target);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return set_err(ctx, MPCQP_ERR_HIP, std::string("leg-torque launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched(ctx, "leg-torque launch");
 }
 
 int mpcqp_leg_torques(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const int32_t* tick,
@@ -1365,10 +1393,7 @@ static int launch_kinematics(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int r
   hipLaunchKernelGGL(mpcqp_kinematics_kernel, dim3((batch + kKinRobots - 1) / kKinRobots), dim3(kKinThreads), 0,
                      (hipStream_t)stream, kp, (int)batch, quat, pos, vel, omega, rot, q, qdot, geom, feet, thighs,
                      pos_feet, foot_pos_base, foot_vel_base, jac);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return set_err(ctx, MPCQP_ERR_HIP, std::string("kinematics launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched(ctx, "kinematics launch");
 }
 
 int mpcqp_kinematics(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* quat, const float* pos,
@@ -1407,24 +1432,14 @@ int mpcqp_step(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t iter_counte
   const bool mpc = (flags & MPCQP_STEP_MPC) != 0;
   if (mpc && (!height_des || !robot || !xref || !contact || !feet))
     return set_err(ctx, MPCQP_ERR_ARG, "null height/robot/xref/contact/feet pointer on an MPC tick");
-  if ((uintptr_t)swing_mem & 15) return set_err(ctx, MPCQP_ERR_ARG, "swing_mem is not 16-byte aligned");
+  if (int rc = aligned16(ctx, swing_mem, "swing_mem")) return rc;
   DeviceScope dev(ctx->device);
   if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
   StepParams sp;
   sp.N = ctx->params.horizon;
   sp.dt = ctx->params.dt;
   sp.max_pos_error = ctx->max_pos_error;
-  sp.sw.ibm = iterations_between_mpc;
-  sp.sw.root_layout = 1;
-  sp.sw.dt_control = ctx->dt_control;
-  sp.sw.gravity = ctx->gravity;
-  sp.sw.swing_height = ctx->swing_height;
-  sp.sw.touchdown_z = ctx->touchdown_z;
-  sp.sw.vel_gain = ctx->vel_gain;
-  memcpy(sp.sw.Kp, ctx->kp_swing, sizeof(sp.sw.Kp));
-  memcpy(sp.sw.Kd, ctx->kd_swing, sizeof(sp.sw.Kd));
-  sp.sw.ground = ctx->ground;
-  sp.sw.ground_cap = ctx->ground_cap;
+  sp.sw = swing_params(ctx, iterations_between_mpc, 1);
   const dim3 grid((batch + kStepRobots - 1) / kStepRobots), block(kStepThreads);
   hipStream_t st = (hipStream_t)stream;
   auto launch = [&](auto kern, const char* what) -> int {
@@ -1432,16 +1447,14 @@ int mpcqp_step(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t iter_counte
                        geom, vel_body_des, yaw_rate_des, gait, height_des, plan_state, swing_mem, x0, xref, contact,
                        feet, (const float*)u0, tau, thighs, pos_feet, foot_pos_base, foot_vel_base, jac,
                        swing_state, pos_target, vel_target);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string(what) + hipGetErrorString(e));
-    return MPCQP_OK;
+    return launched(ctx, what);
   };
-  if (!mpc) return launch(mpcqp_step_kernel<STEP_WHOLE>, "step launch: ");
-  int rc = launch(mpcqp_step_kernel<STEP_FRONT>, "step launch (front): ");
+  if (!mpc) return launch(mpcqp_step_kernel<STEP_WHOLE>, "step launch");
+  int rc = launch(mpcqp_step_kernel<STEP_FRONT>, "step launch (front)");
   if (rc != MPCQP_OK) return rc;
   rc = enqueue_solve(ctx, batch, x0, xref, contact, feet, robot, u0, nullptr, status, iters, stream);
   if (rc != MPCQP_OK) return rc;
-  return launch(mpcqp_step_kernel<STEP_BACK>, "step launch (back): ");
+  return launch(mpcqp_step_kernel<STEP_BACK>, "step launch (back)");
 }
 
 // ---- the base-state estimator (mpcqp_estimator.h): the Kalman filter doc/state_estimation_kf.md
@@ -1451,9 +1464,8 @@ int mpcqp_step(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t iter_counte
 int mpcqp_set_estimator(mpcqp_ctx* ctx, double dt, double gravity, double sigma_p, double sigma_v, double sigma_f,
                         double r_p, double r_v, double r_z, double suspicion, double p0, double contact_height) {
   if (!ctx) return MPCQP_ERR_ARG;
-  const double all[11] = {dt, gravity, sigma_p, sigma_v, sigma_f, r_p, r_v, r_z, suspicion, p0, contact_height};
-  for (double v : all)
-    if (!std::isfinite(v)) return set_err(ctx, MPCQP_ERR_ARG, "non-finite estimator constant");
+  if (!all_finite({dt, gravity, sigma_p, sigma_v, sigma_f, r_p, r_v, r_z, suspicion, p0, contact_height}))
+    return set_err(ctx, MPCQP_ERR_ARG, "non-finite estimator constant");
   if (!(dt > 0.0)) return set_err(ctx, MPCQP_ERR_ARG, "estimator: dt <= 0");
   if (!(r_p > 0.0) || !(r_v > 0.0) || !(r_z > 0.0) || !(p0 > 0.0))
     return set_err(ctx, MPCQP_ERR_ARG, "estimator: r_p, r_v, r_z and p0 must be > 0");
@@ -1472,8 +1484,7 @@ int mpcqp_estimate(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* qu
   const int dof_layout = (flags & MPCQP_EST_DOF_STATES) ? 1 : 0;
   if (!quat || !gyro || !accel || !q || (!dof_layout && !qdot) || !trust || !geom || !est_state)
     return set_err(ctx, MPCQP_ERR_ARG, "null estimator input/state pointer");
-  if ((uintptr_t)est_state & 15) return set_err(ctx, MPCQP_ERR_ARG, "est_state is not 16-byte aligned");
-  static_assert(EST_STRIDE == MPCQP_EST_STRIDE, "record stride");
+  if (int rc = aligned16(ctx, est_state, "est_state")) return rc;
   DeviceScope dev(ctx->device);
   if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
   EstParams ep = ctx->est;
@@ -1481,9 +1492,7 @@ int mpcqp_estimate(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* qu
   hipLaunchKernelGGL(mpcqp_estimate_kernel, dim3((batch + kEstRobots - 1) / kEstRobots), dim3(kEstThreads), 0,
                      (hipStream_t)stream, ep, (int)batch, quat, gyro, accel, q, qdot, trust, geom, est_state,
                      root_states, feet_world, status);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("estimator launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched(ctx, "estimator launch");
 }
 
 // ---- the orientation filter and the contact trust (mpcqp_attitude.h): the first stage of
@@ -1493,9 +1502,8 @@ int mpcqp_estimate(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* qu
 int mpcqp_set_attitude(mpcqp_ctx* ctx, double dt, double gravity, double kappa_ref, double bias_gain,
                        double trust_window, double touch_threshold) {
   if (!ctx) return MPCQP_ERR_ARG;
-  const double all[6] = {dt, gravity, kappa_ref, bias_gain, trust_window, touch_threshold};
-  for (double v : all)
-    if (!std::isfinite(v)) return set_err(ctx, MPCQP_ERR_ARG, "non-finite attitude constant");
+  if (!all_finite({dt, gravity, kappa_ref, bias_gain, trust_window, touch_threshold}))
+    return set_err(ctx, MPCQP_ERR_ARG, "non-finite attitude constant");
   if (!(dt > 0.0) || !(gravity > 0.0)) return set_err(ctx, MPCQP_ERR_ARG, "attitude: dt and gravity must be > 0");
   if (kappa_ref < 0.0 || bias_gain < 0.0) return set_err(ctx, MPCQP_ERR_ARG, "attitude: kappa_ref or bias_gain is < 0");
   if (trust_window < 0.0 || trust_window > 0.5)
@@ -1511,21 +1519,17 @@ int mpcqp_attitude(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* gy
   if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown attitude flags");
   if (batch <= 0) return set_err(ctx, MPCQP_ERR_ARG, "attitude: batch <= 0");
   if (!gyro || !accel || !att_state) return set_err(ctx, MPCQP_ERR_ARG, "null attitude input/state pointer");
-  if ((uintptr_t)att_state & 15) return set_err(ctx, MPCQP_ERR_ARG, "att_state is not 16-byte aligned");
+  if (int rc = aligned16(ctx, att_state, "att_state")) return rc;
   if (gait && !tick) return set_err(ctx, MPCQP_ERR_ARG, "attitude: gait given without tick");
   if (trust && !gait && !touch)
     return set_err(ctx, MPCQP_ERR_ARG, "attitude: trust wanted with neither gait and tick nor touch");
   if (gait && iterations_between_mpc < 1) return set_err(ctx, MPCQP_ERR_ARG, "attitude: iterations_between_mpc < 1");
-  static_assert(ATT_STRIDE == MPCQP_ATT_STRIDE, "record stride");
-  static_assert(ATT_STATUS_OK == MPCQP_STATUS_OK && ATT_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
   DeviceScope dev(ctx->device);
   if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
   hipLaunchKernelGGL(mpcqp_attitude_kernel, dim3((batch + kAttThreads - 1) / kAttThreads), dim3(kAttThreads), 0,
                      (hipStream_t)stream, ctx->att, (int)batch, (int)iterations_between_mpc, gyro, accel, tick, gait,
                      touch, att_state, quat, gyro_out, trust, status);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("attitude launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched(ctx, "attitude launch");
 }
 
 // ---- the terrain plane (mpcqp_terrain.h): RobotData.update_terrain_normal (robot_data.py:186-228)
@@ -1533,9 +1537,8 @@ int mpcqp_attitude(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* gy
 // An invalid constant leaves the previous set in force.
 int mpcqp_set_terrain(mpcqp_ctx* ctx, double contact_threshold, double flat_tol, double cos_max_tilt, double blend) {
   if (!ctx) return MPCQP_ERR_ARG;
-  const double all[4] = {contact_threshold, flat_tol, cos_max_tilt, blend};
-  for (double v : all)
-    if (!std::isfinite(v)) return set_err(ctx, MPCQP_ERR_ARG, "non-finite terrain constant");
+  if (!all_finite({contact_threshold, flat_tol, cos_max_tilt, blend}))
+    return set_err(ctx, MPCQP_ERR_ARG, "non-finite terrain constant");
   if (flat_tol < 0.0 || !(flat_tol < 1.0)) return set_err(ctx, MPCQP_ERR_ARG, "terrain: flat_tol outside [0, 1)");
   if (!(cos_max_tilt > 0.0) || cos_max_tilt > 1.0)
     return set_err(ctx, MPCQP_ERR_ARG, "terrain: cos_max_tilt outside (0, 1]");
@@ -1562,14 +1565,9 @@ int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos
   if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "terrain: batch < 0");
   if (!pos_feet || !contact || !terrain_state)
     return set_err(ctx, MPCQP_ERR_ARG, "null terrain input/state pointer");
-  if ((uintptr_t)terrain_state & 15) return set_err(ctx, MPCQP_ERR_ARG, "terrain_state is not 16-byte aligned");
+  if (int rc = aligned16(ctx, terrain_state, "terrain_state")) return rc;
   if (normal_base && !quat) return set_err(ctx, MPCQP_ERR_ARG, "terrain: normal_base wanted without quat");
   if (batch == 0) return MPCQP_OK;
-  static_assert(TER_STRIDE == MPCQP_TERRAIN_STRIDE, "record stride");
-  static_assert(TER_ROBOT_STRIDE == MPCQP_ROBOT_STRIDE && TER_ROBOT_NORMAL == MPCQP_ROBOT_NORMAL &&
-                    MPCQP_ROBOT_NORMAL + 3 <= MPCQP_ROBOT_STRIDE, "the normal's words of the robot record");
-  static_assert(TER_SWING_STATE == MPCQP_TERRAIN_SWING_STATE && TER_ROOT_STATES == MPCQP_TERRAIN_ROOT_STATES, "flags");
-  static_assert(TER_STATUS_OK == MPCQP_STATUS_OK && TER_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
   DeviceScope dev(ctx->device);
   if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
   TerParams tp = ctx->ter;
@@ -1577,9 +1575,7 @@ int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos
   hipLaunchKernelGGL(mpcqp_terrain_kernel, dim3((batch + kTerThreads - 1) / kTerThreads), dim3(kTerThreads), 0,
                      (hipStream_t)stream, tp, (int)batch, pos_feet, contact, quat, terrain_state, robot, normal, plane,
                      normal_base, status);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(ctx, MPCQP_ERR_HIP, std::string("terrain launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched(ctx, "terrain launch");
 }
 
 int mpcqp_destroy(mpcqp_ctx* ctx) {

@@ -24,37 +24,6 @@ STATUS_UNSUPPORTED = 5
 ROBOT_STRIDE = 16
 MAX_HORIZON = 32    # MPCQP_MAX_HORIZON: mpcqp_create rejects a longer horizon
 
-# every symbol declared in include/mpcqp.h
-EXPORTED_SYMBOLS = (
-    "mpcqp_abi_version",
-    "mpcqp_default_params",
-    "mpcqp_create",
-    "mpcqp_solve",
-    "mpcqp_set_stance_hint",
-    "mpcqp_set_stance_range",
-    "mpcqp_set_order",
-    "mpcqp_set_weights",
-    "mpcqp_set_warm_start",
-    "mpcqp_destroy",
-    "mpcqp_last_error",
-    "mpcqp_plan",
-    "mpcqp_plan_root_states",
-    "mpcqp_set_planner",
-    "mpcqp_stance_torques",
-    "mpcqp_leg_torques",
-    "mpcqp_leg_torques_root_states",
-    "mpcqp_set_swing",
-    "mpcqp_kinematics",
-    "mpcqp_kinematics_root_states",
-    "mpcqp_step",
-    "mpcqp_estimate",
-    "mpcqp_set_estimator",
-    "mpcqp_attitude",
-    "mpcqp_set_attitude",
-    "mpcqp_terrain",
-    "mpcqp_set_terrain",
-    "mpcqp_set_ground",
-)
 ABI_VERSION = 6
 WARM_BYTES = 128     # MPCQP_WARM_BYTES: warm-start memory per robot
 PLAN_STRIDE = 8     # MPCQP_PLAN_STRIDE: float64 planner state per robot
@@ -83,6 +52,45 @@ class MpcqpParams(ctypes.Structure):
     ]
 
 
+_vp, _i32, _int, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int, ctypes.c_double
+_params_p = ctypes.POINTER(MpcqpParams)
+
+# The ABI, one row per function declared in include/mpcqp.h: symbol -> (restype, argtypes).
+# The context, the stream and every device or host array travel as void pointers
+# (tests/test_abi.py holds each row to its declaration, position by position).
+SIGNATURES = {
+    "mpcqp_abi_version": (_i32, []),
+    "mpcqp_default_params": (None, [_params_p, _i32]),
+    "mpcqp_create": (_int, [_params_p, _i32, ctypes.POINTER(_vp)]),
+    "mpcqp_solve": (_int, [_vp, _i32] + [_vp] * 10),
+    "mpcqp_set_stance_hint": (_int, [_vp, _i32]),
+    "mpcqp_set_stance_range": (_int, [_vp, _i32, _i32]),
+    "mpcqp_set_order": (_int, [_vp, _i32]),
+    "mpcqp_set_weights": (_int, [_vp, _vp, _vp]),
+    "mpcqp_set_warm_start": (_int, [_vp, _vp, _i32]),
+    "mpcqp_destroy": (_int, [_vp]),
+    "mpcqp_last_error": (ctypes.c_char_p, [_vp]),
+    "mpcqp_plan": (_int, [_vp, _i32, _i32] + [_vp] * 15),
+    "mpcqp_plan_root_states": (_int, [_vp, _i32, _i32] + [_vp] * 11),
+    "mpcqp_set_planner": (_int, [_vp, _f64, _f64, _f64]),
+    "mpcqp_stance_torques": (_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "mpcqp_leg_torques": (_int, [_vp, _i32, _i32, _vp, _i32] + [_vp] * 19),
+    "mpcqp_leg_torques_root_states": (_int, [_vp, _i32, _i32, _vp, _i32] + [_vp] * 16),
+    "mpcqp_set_swing": (_int, [_vp, _f64, _vp, _vp, _f64, _f64]),
+    "mpcqp_kinematics": (_int, [_vp, _i32, _i32] + [_vp] * 15),
+    "mpcqp_kinematics_root_states": (_int, [_vp, _i32, _i32] + [_vp] * 10),
+    "mpcqp_step": (_int, [_vp, _i32, _i32, _i32, _vp, _i32] + [_vp] * 27),
+    "mpcqp_estimate": (_int, [_vp, _i32, _i32] + [_vp] * 12),
+    "mpcqp_set_estimator": (_int, [_vp] + [_f64] * 11),
+    "mpcqp_attitude": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32] + [_vp] * 8),
+    "mpcqp_set_attitude": (_int, [_vp] + [_f64] * 6),
+    "mpcqp_terrain": (_int, [_vp, _i32, _i32] + [_vp] * 10),
+    "mpcqp_set_terrain": (_int, [_vp] + [_f64] * 4),
+    "mpcqp_set_ground": (_int, [_vp, _vp, _i32]),
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)   # every symbol declared in include/mpcqp.h
+
+
 class MpcqpError(RuntimeError):
     pass
 
@@ -99,63 +107,9 @@ def load():
         raise MpcqpError(f"{LIB_PATH} not built: run __graft_entry__.build() "
                          "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    vp, i32, f32p, i32p = ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p
-    lib.mpcqp_abi_version.restype = i32
-    lib.mpcqp_abi_version.argtypes = []
-    lib.mpcqp_default_params.restype = None
-    lib.mpcqp_default_params.argtypes = [ctypes.POINTER(MpcqpParams), i32]
-    lib.mpcqp_create.restype = ctypes.c_int
-    lib.mpcqp_create.argtypes = [ctypes.POINTER(MpcqpParams), i32, ctypes.POINTER(vp)]
-    lib.mpcqp_solve.restype = ctypes.c_int
-    lib.mpcqp_solve.argtypes = [vp, i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32p, i32p, vp]
-    lib.mpcqp_set_stance_hint.restype = ctypes.c_int
-    lib.mpcqp_set_stance_hint.argtypes = [vp, i32]
-    lib.mpcqp_set_stance_range.restype = ctypes.c_int
-    lib.mpcqp_set_stance_range.argtypes = [vp, i32, i32]
-    lib.mpcqp_set_order.restype = ctypes.c_int
-    lib.mpcqp_set_order.argtypes = [vp, i32]
-    lib.mpcqp_set_weights.restype = ctypes.c_int
-    lib.mpcqp_set_weights.argtypes = [vp, vp, vp]
-    lib.mpcqp_set_warm_start.restype = ctypes.c_int
-    lib.mpcqp_set_warm_start.argtypes = [vp, vp, i32]
-    lib.mpcqp_destroy.restype = ctypes.c_int
-    lib.mpcqp_destroy.argtypes = [vp]
-    lib.mpcqp_last_error.restype = ctypes.c_char_p
-    lib.mpcqp_last_error.argtypes = [vp]
-    lib.mpcqp_plan.restype = ctypes.c_int
-    lib.mpcqp_plan.argtypes = [vp, i32, i32] + [vp] * 14 + [vp]
-    lib.mpcqp_plan_root_states.restype = ctypes.c_int
-    lib.mpcqp_plan_root_states.argtypes = [vp, i32, i32] + [vp] * 10 + [vp]
-    lib.mpcqp_set_planner.restype = ctypes.c_int
-    lib.mpcqp_set_planner.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
-    lib.mpcqp_stance_torques.restype = ctypes.c_int
-    lib.mpcqp_stance_torques.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
-    lib.mpcqp_leg_torques.restype = ctypes.c_int
-    lib.mpcqp_leg_torques.argtypes = [vp, i32, i32, vp, i32] + [vp] * 18 + [vp]
-    lib.mpcqp_leg_torques_root_states.restype = ctypes.c_int
-    lib.mpcqp_leg_torques_root_states.argtypes = [vp, i32, i32, vp, i32] + [vp] * 15 + [vp]
-    lib.mpcqp_set_swing.restype = ctypes.c_int
-    lib.mpcqp_set_swing.argtypes = [vp, ctypes.c_double, vp, vp, ctypes.c_double, ctypes.c_double]
-    lib.mpcqp_kinematics.restype = ctypes.c_int
-    lib.mpcqp_kinematics.argtypes = [vp, i32, i32] + [vp] * 14 + [vp]
-    lib.mpcqp_kinematics_root_states.restype = ctypes.c_int
-    lib.mpcqp_kinematics_root_states.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
-    lib.mpcqp_step.restype = ctypes.c_int
-    lib.mpcqp_step.argtypes = [vp, i32, i32, i32, vp, i32] + [vp] * 26 + [vp]
-    lib.mpcqp_estimate.restype = ctypes.c_int
-    lib.mpcqp_estimate.argtypes = [vp, i32, i32] + [vp] * 11 + [vp]
-    lib.mpcqp_set_estimator.restype = ctypes.c_int
-    lib.mpcqp_set_estimator.argtypes = [vp] + [ctypes.c_double] * 11
-    lib.mpcqp_attitude.restype = ctypes.c_int
-    lib.mpcqp_attitude.argtypes = [vp, i32, i32, vp, vp, vp, i32] + [vp] * 7 + [vp]
-    lib.mpcqp_set_attitude.restype = ctypes.c_int
-    lib.mpcqp_set_attitude.argtypes = [vp] + [ctypes.c_double] * 6
-    lib.mpcqp_terrain.restype = ctypes.c_int
-    lib.mpcqp_terrain.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
-    lib.mpcqp_set_terrain.restype = ctypes.c_int
-    lib.mpcqp_set_terrain.argtypes = [vp] + [ctypes.c_double] * 4
-    lib.mpcqp_set_ground.restype = ctypes.c_int
-    lib.mpcqp_set_ground.argtypes = [vp, vp, i32]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise MpcqpError("libmpcqp ABI version mismatch")
     _lib = lib

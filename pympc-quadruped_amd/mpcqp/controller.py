@@ -138,6 +138,13 @@ class BatchedController:
             self.plan_state[robots] = 0.0
             self.swing_mem[robots] = 0.0
 
+    def _f32(self, t):
+        """``t`` as a contiguous float32 tensor on the device: ``t`` itself, with no copy, when
+        it already is one."""
+        if t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device:
+            return t
+        return t.to(self.device, torch.float32).contiguous()
+
     def _cmd(self, v, shape):
         t = torch.as_tensor(v, dtype=torch.float64)
         return t.to(self.device).expand(shape).contiguous()
@@ -159,19 +166,18 @@ class BatchedController:
         vb = self._cmd(vel_body_des, (B, 3))
         yr = self._cmd(yaw_rate_des, (B,))
         if root_states is not None:
-            rs = root_states if root_states.dtype == torch.float32 and root_states.is_contiguous() \
-                else root_states.to(torch.float32).contiguous()
+            rs = self._f32(root_states)
             self.engine.plan(flags, self.plan_state, self.x0, vb, yr, root_states=rs, gait=self.gait,
                              iteration=self.iteration, height_des=self.height, xref=self.xref,
                              contact=self.contact)
         else:
-            c = [t.to(self.device, torch.float32).contiguous() for t in (quat, pos, omega, vel)]
-            r = rot.to(self.device, torch.float32).contiguous() if rot is not None else None
+            c = [self._f32(t) for t in (quat, pos, omega, vel)]
+            r = self._f32(rot) if rot is not None else None
             self.engine.plan(flags, self.plan_state, self.x0, vb, yr, quat=c[0], pos=c[1], omega=c[2],
                              vel=c[3], rot=r, gait=self.gait, iteration=self.iteration,
                              height_des=self.height, xref=self.xref, contact=self.contact)
         if mpc_tick:
-            ft = feet.to(self.device, torch.float32).contiguous()
+            ft = self._f32(feet)
             self.engine.solve_raw(B, self.x0, self.xref, self.contact, ft, self.robot, self.u0,
                                   status=self.status, iters=self.iterations)
         return self.u0
@@ -182,8 +188,7 @@ class BatchedController:
         jac [B,4,3,3]: each leg's 3x3 block of its foot Jacobian; stance [B,4] > 0 for
         legs whose swing state is 0 (leg_controller.py:77).  Swing-leg entries of tau
         keep whatever the swing controller wrote."""
-        j = jac.to(self.device, torch.float32).contiguous()
-        s = stance.to(self.device, torch.float32).contiguous()
+        j, s = self._f32(jac), self._f32(stance)
         self.engine.stance_torques(j, s, self.u0, self.tau, stance_stride=s.shape[-1])
         return self.tau
 
@@ -205,17 +210,13 @@ class BatchedController:
             self.tick_count.fill_(int(iter_counter))
         vb = self._cmd(vel_body_des, (B, 3))
         yr = self._cmd(yaw_rate_des, (B,))
-        th, pf, fp, fv, j = [t.to(self.device, torch.float32).contiguous()
-                             for t in (thighs, pos_feet, foot_pos_base, foot_vel_base, jac)]
+        th, pf, fp, fv, j = [self._f32(t) for t in (thighs, pos_feet, foot_pos_base, foot_vel_base, jac)]
         kw = dict(swing_state=self.swing_state, pos_target=self.pos_target, vel_target=self.vel_target)
         if root_states is not None:
-            rs = root_states if root_states.dtype == torch.float32 and root_states.is_contiguous() \
-                else root_states.to(torch.float32).contiguous()
-            kw["root_states"] = rs
+            kw["root_states"] = self._f32(root_states)
         else:
-            c = [t.to(self.device, torch.float32).contiguous() for t in (quat, pos, vel)]
-            kw.update(quat=c[0], pos=c[1], vel=c[2],
-                      rot=rot.to(self.device, torch.float32).contiguous() if rot is not None else None)
+            c = [self._f32(t) for t in (quat, pos, vel)]
+            kw.update(quat=c[0], pos=c[1], vel=c[2], rot=self._f32(rot) if rot is not None else None)
         self.engine.leg_torques(self.tick_count, self.iterations_between_mpc, vb, yr, self.gait, th, pf, fp, fv, j,
                                 self.u0, self.swing_mem, self.tau, **kw)
         return self.tau
@@ -227,8 +228,7 @@ class BatchedController:
         and jac."""
         if self.geometry is None:
             raise ValueError("no leg geometry: pass geometry= (params.LEG_GEOMETRY, leg_geometry_from_urdf)")
-        rs, ds = [t if t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
-                  else t.to(self.device, torch.float32).contiguous() for t in (root_states, dof_states)]
+        rs, ds = self._f32(root_states), self._f32(dof_states)
         if rs.shape != (self.B, 13) or ds.numel() != self.B * 24:
             raise ValueError(f"expected root_states [{self.B},13] and dof_states [{self.B},12,2], got "
                              f"{tuple(rs.shape)} and {tuple(ds.shape)}")
@@ -281,8 +281,7 @@ class BatchedController:
         if self.geometry is None:
             raise ValueError("no leg geometry: pass geometry= (params.LEG_GEOMETRY, leg_geometry_from_urdf)")
         dev, B = self.device, self.B
-        rs, ds = [t if t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
-                  else t.to(dev, torch.float32).contiguous() for t in (root_states, dof_states)]
+        rs, ds = self._f32(root_states), self._f32(dof_states)
         if rs.shape != (B, 13) or ds.numel() != B * 24:
             raise ValueError(f"expected root_states [{B},13] and dof_states [{B},12,2], got "
                              f"{tuple(rs.shape)} and {tuple(ds.shape)}")

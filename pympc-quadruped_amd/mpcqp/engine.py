@@ -179,6 +179,13 @@ class LinearMpc:
                 raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
         return t
 
+    def _stream_ptr(self, stream):
+        """The launch stream of a call as the ABI's ``void* stream``: ``stream``, or the
+        device's current stream for None."""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        return ctypes.c_void_p(stream.cuda_stream)
+
     def solve(self, state, xref, contact_schedule, feet, robot=None, return_all=False, stream=None):
         """Formulate + solve B QPs.
 
@@ -239,11 +246,10 @@ class LinearMpc:
     def solve_raw(self, B, x0, xref, contact, feet, robot, u0, U=None, status=None, iters=None,
                   stream=None):
         """Zero-overhead launch on preallocated contiguous float32 device tensors."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         code = self.lib.mpcqp_solve(self._ctx, int(B), _ptr(x0), _ptr(xref), _ptr(contact),
                                     _ptr(feet), _ptr(robot), _ptr(u0), _ptr(U), _ptr(status),
-                                    _ptr(iters), ctypes.c_void_p(stream.cuda_stream))
+                                    _ptr(iters), s)
         _lib.check(self._ctx, code, "mpcqp_solve")
 
     def bind_solve(self, B, x0, xref, contact, feet, robot, u0, U=None, status=None, iters=None):
@@ -279,10 +285,8 @@ class LinearMpc:
         Every argument is a preallocated contiguous device tensor (float32, except
         plan_state / vel_body_des / yaw_rate_des float64 and gait / iteration int32);
         ``root_states`` [B,13] (Isaac Gym layout) replaces quat/pos/omega/vel/rot."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         B = int(plan_state.shape[0])
-        s = ctypes.c_void_p(stream.cuda_stream)
         if root_states is not None:
             code = self.lib.mpcqp_plan_root_states(
                 self._ctx, B, int(flags), _ptr(root_states), _ptr(vel_body_des), _ptr(yaw_rate_des),
@@ -316,11 +320,10 @@ class LinearMpc:
 
         jac [B,4,3,3] float32 (each leg's 3x3 Jacobian block), stance [B, >=4]
         (> 0 = stance) read with ``stance_stride``, u0 / tau [B,12]."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         B = int(u0.shape[0])
         code = self.lib.mpcqp_stance_torques(self._ctx, B, _ptr(jac), _ptr(stance), int(stance_stride), _ptr(u0),
-                                             _ptr(tau), ctypes.c_void_p(stream.cuda_stream))
+                                             _ptr(tau), s)
         _lib.check(self._ctx, code, "mpcqp_stance_torques")
 
     def set_swing(self, swing_height=0.1, Kp=None, Kd=None, touchdown_z=-0.0255, vel_gain=0.03):
@@ -360,10 +363,8 @@ class LinearMpc:
         [B,4,3,3], u0 / tau [B,12]).  ``root_states`` [B,13] (Isaac Gym layout) replaces
         quat/pos/vel/rot.  swing_state [B,4], pos_target / vel_target [B,4,3] are optional
         outputs."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         B = int(tau.shape[0])
-        s = ctypes.c_void_p(stream.cuda_stream)
         tail = (_ptr(vel_body_des), _ptr(yaw_rate_des), _ptr(gait), _ptr(thighs), _ptr(pos_feet),
                 _ptr(foot_pos_base), _ptr(foot_vel_base), _ptr(jac), _ptr(u0), _ptr(swing_mem), _ptr(tau),
                 _ptr(swing_state), _ptr(pos_target), _ptr(vel_target), s)
@@ -389,11 +390,10 @@ class LinearMpc:
         [B,13] and ``dof_states`` [B,12,2] (Isaac Gym layout) in their place.  Outputs, each
         optional: feet, thighs, pos_feet, foot_pos_base, foot_vel_base [B,4,3], jac
         [B,4,3,3]."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         B = int(geom.shape[0])
         tail = (_ptr(geom), _ptr(feet), _ptr(thighs), _ptr(pos_feet), _ptr(foot_pos_base), _ptr(foot_vel_base),
-                _ptr(jac), ctypes.c_void_p(stream.cuda_stream))
+                _ptr(jac), s)
         if (root_states is None) != (dof_states is None):
             raise ValueError("kinematics: root_states and dof_states go together")
         if root_states is not None:
@@ -492,15 +492,14 @@ class LinearMpc:
         ``dof_states`` [B,12,2] in their place.  Outputs, each optional: root_states [B,13]
         (Isaac Gym layout, what the ``*_root_states`` calls read), feet_world [B,4,3],
         status [B]."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         if (dof_states is None) == (q is None):
             raise ValueError("estimate: give q and qdot, or dof_states")
         B = int(est_state.shape[0])
         flags, jq, jqd = (_lib.EST_DOF_STATES, dof_states, None) if dof_states is not None else (0, q, qdot)
         code = self.lib.mpcqp_estimate(self._ctx, B, flags, _ptr(quat), _ptr(gyro), _ptr(accel), _ptr(jq), _ptr(jqd),
                                        _ptr(trust), _ptr(geom), _ptr(est_state), _ptr(root_states),
-                                       _ptr(feet_world), _ptr(status), ctypes.c_void_p(stream.cuda_stream))
+                                       _ptr(feet_world), _ptr(status), s)
         _lib.check(self._ctx, code, "mpcqp_estimate")
 
     def set_attitude(self, dt=0.001, gravity=9.81, kappa_ref=0.1, bias_gain=0.0, trust_window=0.2,
@@ -527,13 +526,11 @@ class LinearMpc:
         accel [B,3] (body frame); for the trust, tick and gait with ``iterations_between_mpc``
         (as for ``leg_torques``) and / or touch [B,4].  Outputs, each optional: quat [B,4]
         (w, x, y, z), gyro_out [B,3] (gyro less the estimated bias), trust [B,4], status [B]."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         B = int(att_state.shape[0])
         code = self.lib.mpcqp_attitude(self._ctx, B, 0, _ptr(gyro), _ptr(accel), _ptr(tick),
                                        int(iterations_between_mpc), _ptr(gait), _ptr(touch), _ptr(att_state),
-                                       _ptr(quat), _ptr(gyro_out), _ptr(trust), _ptr(status),
-                                       ctypes.c_void_p(stream.cuda_stream))
+                                       _ptr(quat), _ptr(gyro_out), _ptr(trust), _ptr(status), s)
         _lib.check(self._ctx, code, "mpcqp_attitude")
 
     def set_terrain(self, contact_threshold=0.5, flat_tol=1e-3, cos_max_tilt=0.5, blend=1.0):
@@ -577,8 +574,7 @@ class LinearMpc:
         normal, are overwritten.  Outputs, each optional: normal [B,3], plane [B,4] (n, d),
         normal_base [B,3], status [B].  A tensor of another size, dtype or device, or one
         that is not contiguous, raises ValueError: the kernel reads and writes B rows of each."""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
+        s = self._stream_ptr(stream)
         if (contact is None) == (swing_state is None):
             raise ValueError("terrain: give contact or swing_state")
         if quat is not None and root_states is not None:
@@ -609,5 +605,5 @@ class LinearMpc:
             flags, quat = flags | _lib.TERRAIN_ROOT_STATES, root_states
         code = self.lib.mpcqp_terrain(self._ctx, B, flags, _ptr(pos_feet), _ptr(contact), _ptr(quat),
                                       _ptr(terrain_state), _ptr(robot), _ptr(normal), _ptr(plane),
-                                      _ptr(normal_base), _ptr(status), ctypes.c_void_p(stream.cuda_stream))
+                                      _ptr(normal_base), _ptr(status), s)
         _lib.check(self._ctx, code, "mpcqp_terrain")

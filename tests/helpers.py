@@ -1,8 +1,20 @@
-"""Shared test helpers: oracle solutions for synthetic batches (CPU, float64)."""
+"""Shared test helpers: oracle solutions for synthetic batches (CPU, float64), and the
+symbols include/mpcqp.h declares."""
+import os
+import re
+
 import numpy as np
 
 from oracle import formulation as F
 from oracle import qp as QP
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mpcqp.h")
+
+
+def _declared():
+    """The name of every function include/mpcqp.h declares."""
+    src = open(HEADER).read()
+    return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
 
 
 def oracle_solution(batch, b, horizon, Q=F.Q_DIAG, R=F.R_DIAG):

@@ -6,18 +6,66 @@ import re
 
 import pytest
 
+from helpers import _declared
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 
 
-def _declared():
-    src = open(HEADER).read()
-    return sorted(set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M)))
-
-
 def test_header_and_binding_agree():
     from mpcqp import _lib
-    assert _declared() == sorted(_lib.EXPORTED_SYMBOLS)
+    assert sorted(_declared()) == sorted(_lib.EXPORTED_SYMBOLS)
+
+
+def _prototypes():
+    """{name: (return type, [parameter types])} of include/mpcqp.h, comments removed; a type is
+    the declaration's text less the parameter's name, "T*" for every pointer."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(mpcqp_\w+)\s*\(([^)]*)\)\s*;", src, re.M):
+        kinds = []
+        for prm in params.split(","):
+            prm = " ".join(prm.split())
+            if prm == "void" and "," not in params:
+                continue
+            kinds.append("T*" if "*" in prm else re.sub(r"\s*\w+$", "", prm))
+        out[name] = ("T*" if "*" in ret else ret.strip(), kinds)
+    return out
+
+
+def _is_pointer(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def _is_int32(t):
+    return t in (ctypes.c_int32, ctypes.c_int) and ctypes.sizeof(t) == 4
+
+
+def test_binding_signatures_match_the_header():
+    """Every row of the binding table agrees with its declaration in include/mpcqp.h position by
+    position: a pointer is passed as a pointer, int32_t as a 32-bit int, double as c_double, and
+    the return type likewise.  A miscounted row would hand a kernel garbage pointers."""
+    from mpcqp import _lib
+    protos = _prototypes()
+    assert set(protos) == _declared() == set(_lib.SIGNATURES) and len(protos) == 28
+    agrees = {"T*": _is_pointer, "int32_t": _is_int32, "int": _is_int32, "double": lambda t: t is ctypes.c_double}
+    for name, (ret, kinds) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert len(argtypes) == len(kinds), (name, len(argtypes), len(kinds))
+        for i, (kind, t) in enumerate(zip(kinds, argtypes)):
+            assert kind in agrees, (name, i, kind)
+            assert agrees[kind](t), (name, i, kind, t)
+        if ret == "void":
+            assert restype is None, name
+        elif ret == "T*":
+            assert restype is ctypes.c_char_p, name      # the one pointer returned: mpcqp_last_error's text
+        else:
+            assert ret in ("int", "int32_t") and _is_int32(restype), (name, ret, restype)
+    # the table is what load() applies
+    lib = _lib.load()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
 
 
 def test_library_exports_every_declared_symbol():

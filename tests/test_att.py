@@ -28,6 +28,7 @@ import pytest
 
 import att_edge_checks
 import att_ref
+from helpers import _declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
@@ -59,11 +60,6 @@ extern "C" int decide(int tick, int ibm, int period, int off, int dur) {
 }
 extern "C" int stride(void) { return ATT_STRIDE; }
 '''
-
-
-def _declared():
-    src = open(HEADER).read()
-    return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
 
 
 def test_header_declares_the_attitude_entry_points_and_binding_agrees():

@@ -33,6 +33,7 @@ import pytest
 
 import est_ref
 import kin_ref
+from helpers import _declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
@@ -80,11 +81,6 @@ extern "C" void launch(const double* c, int dof, int B, const float* quat, const
 extern "C" int robots_per_workgroup(void) { return kEstRobots; }
 extern "C" int stride(void) { return EST_STRIDE; }
 '''
-
-
-def _declared():
-    src = open(HEADER).read()
-    return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
 
 
 def test_header_declares_the_estimator_entry_points_and_binding_agrees():

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import _declared
 import kin_edge_checks
 import kin_ref
 
@@ -50,11 +51,6 @@ extern "C" int stride(void) { return KIN_STRIDE; }
 '''
 
 NEW_SYMBOLS = {"mpcqp_kinematics", "mpcqp_kinematics_root_states"}
-
-
-def _declared():
-    src = open(HEADER).read()
-    return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
 
 
 def test_header_declares_the_kinematics_entry_points_and_binding_agrees():

@@ -16,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import _declared
 import swing_ref
 from swing_ref import SwingRef, quat2matrix_f32
 
@@ -62,11 +63,6 @@ extern "C" int leg_tick(int tick, int ibm, const int* gait, int leg, const doubl
   return st;
 }
 '''
-
-
-def _declared():
-    src = open(HEADER).read()
-    return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
 
 
 NEW_SYMBOLS = {"mpcqp_leg_torques", "mpcqp_leg_torques_root_states", "mpcqp_set_swing"}

@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 import terrain_ref as tr
+from helpers import _declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
@@ -65,11 +66,6 @@ extern "C" void leg_step(int which, double* mem, const double* in, const double*
                           in[30], in[31], in[32], pb, vb, ground);
 }
 '''
-
-
-def _declared():
-    src = open(HEADER).read()
-    return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
 
 
 def test_header_declares_the_terrain_entry_points_and_binding_agrees():
