@@ -636,6 +636,9 @@ int mpcqp_set_terrain(mpcqp_ctx* ctx, double contact_threshold, double flat_tol,
  * disables; capacity < 0, or a NULL plane with capacity > 0, returns MPCQP_ERR_ARG. */
 int mpcqp_set_ground(mpcqp_ctx* ctx, const float* plane, int32_t capacity);
 
+/* The predicted trajectory of a force sequence, its cost and cone margin (mpcqp_predict) are
+ * declared in mpcqp_predict_abi.h, which includes this file. */
+
 int mpcqp_destroy(mpcqp_ctx* ctx);
 
 const char* mpcqp_last_error(const mpcqp_ctx* ctx);

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "mpcqp.h"
+#include "mpcqp_predict_abi.h"
 
 namespace {
 
@@ -356,6 +357,7 @@ constexpr int kPrioTab = 4096;
 #include "mpcqp_estimator.h"
 #include "mpcqp_attitude.h"
 #include "mpcqp_terrain.h"
+#include "mpcqp_predict.h"
 // the kernel headers' constants are those of include/mpcqp.h
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 static_assert(EST_STRIDE == MPCQP_EST_STRIDE, "estimator record stride");
@@ -1576,6 +1578,39 @@ int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos
                      (hipStream_t)stream, tp, (int)batch, pos_feet, contact, quat, terrain_state, robot, normal, plane,
                      normal_base, status);
   return launched(ctx, "terrain launch");
+}
+
+// The trajectory the QP believes a force sequence produces (com_traj = Sx x0 + Su U,
+// mpc.py:293-294), its cost, cone margin and swing residual: one launch, one wavefront per robot.
+int mpcqp_predict(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0, const float* xref,
+                  const float* contact, const float* feet, const float* robot, const float* U, float* X,
+                  double* report, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown predict flags");
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "predict: batch < 0");
+  if (!x0 || !xref || !contact || !feet || !robot || !U)
+    return set_err(ctx, MPCQP_ERR_ARG, "null predict input pointer");
+  if (batch == 0 || (!X && !report && !status)) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  KParams kp;
+  kp.N = ctx->params.horizon;
+  kp.max_iter = 0;
+  kp.dt = ctx->params.dt;
+  for (int i = 0; i < NX; ++i) kp.q[i] = ctx->params.q_diag[i];
+  for (int i = 0; i < NU; ++i) kp.r[i] = ctx->params.r_diag[i];
+  kp.wfull = ctx->wdev;
+  kp.warm = nullptr;
+  kp.warm_cap = 0;
+  const bool full = kp.wfull != nullptr;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(LANES), 0, (hipStream_t)stream, kp, (int)batch, x0, xref, contact, feet,
+                       robot, U, X, report, status);
+  };
+  // the instantiation whose LDS holds this horizon and these weights
+  if (kp.N <= 16) full ? launch(mpcqp_predict_kernel<16, true>) : launch(mpcqp_predict_kernel<16, false>);
+  else full ? launch(mpcqp_predict_kernel<kMaxN, true>) : launch(mpcqp_predict_kernel<kMaxN, false>);
+  return launched(ctx, "predict launch");
 }
 
 int mpcqp_destroy(mpcqp_ctx* ctx) {

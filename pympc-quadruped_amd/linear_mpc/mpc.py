@@ -270,6 +270,30 @@ class ModelPredictiveController():
             self._ref_traj_host = self._dev["xref"].cpu().numpy().reshape(-1)
         return self._ref_traj_host
 
+    def predicted_trajectory(self):
+        """com_traj of the last MPC tick (mpc.py:293-294: Sx @ xt + Su @ contact_forces, what the
+        reference's debug branch of update_mpc_if_needed plots), float32 (N, 13): row t is the
+        state the QP expects at step t + 1.  Computed on the device (mpcqp_predict) from the
+        buffers that tick left -- its x0, X_ref, gait table, foot positions and U -- so call it
+        after the tick and before the next control iteration repacks x0.  Raises RuntimeError
+        before the first MPC tick."""
+        import torch
+        if self._engine is None or not self._solve_fns or self._up_views is None:
+            raise RuntimeError("predicted_trajectory: no MPC tick has run yet")
+        e, dv, up = self._engine, self._dev, self._up_views
+        N = self.horizon
+        X = dv.get("X_pred")
+        if X is None:
+            X = dv["X_pred"] = torch.zeros((1, N, 13), dtype=torch.float32, device=e.device)
+            dv["status_pred"] = torch.zeros((1,), dtype=torch.int32, device=e.device)
+            self._predict_fn = e.bind_predict(1, dv["x0"], dv["xref"], up["contact"].reshape(1, N, 4), up["feet"],
+                                              dv["robot"], dv["U"].reshape(1, N, 12), X, None, dv["status_pred"])
+        self._predict_fn(torch.cuda.current_stream(e.device))
+        out = X.cpu().numpy()[0]
+        if int(dv["status_pred"].cpu()[0]) != 0:
+            raise RuntimeError("mpcqp: predicted trajectory is not finite")
+        return out
+
     def generate_reference_trajectory(self, vel_base_des, yaw_turn_rate):
         """mpc.py:110-170 alone (stateful clamp + roll/pitch compensation), on the device.
 

@@ -46,6 +46,19 @@ class SolveResult:
         self.u0, self.U, self.status, self.iterations = u0, U, status, iters
 
 
+class PredictResult:
+    """What ``LinearMpc.predict`` returns (include/mpcqp_predict_abi.h mpcqp_predict), device tensors: X
+    [B,N,13] float32, the predicted states x_1 .. x_N; cost, cost_free, cone_margin and
+    swing_residual [B] float64, views of the one ``report`` tensor [B,PREDICT_REPORT]; status [B]
+    int32 (STATUS_OK or STATUS_NONFINITE, whose X and report are zeros).  ``cost - cost_free`` is
+    the QP's objective 1/2 U^T H U + g^T U."""
+
+    def __init__(self, X, report, status):
+        self.X, self.report, self.status = X, report, status
+        self.cost, self.cost_free = report[:, 0], report[:, 1]
+        self.cone_margin, self.swing_residual = report[:, 2], report[:, 3]
+
+
 class LinearMpc:
     """Batched reference MPC: one QP per robot, solved on one MI355X.
 
@@ -263,6 +276,89 @@ class LinearMpc:
 
         def launch(stream):
             _lib.check(ctx, lib.mpcqp_solve(*args, ctypes.c_void_p(stream.cuda_stream)), "mpcqp_solve")
+        launch.buffers = keep
+        return launch
+
+    def predict(self, state, xref, contact_schedule, feet, U, robot=None, stream=None):
+        """The trajectory the QP believes the force sequence ``U`` produces, its tracking cost,
+        cone margin and swing residual (include/mpcqp_predict_abi.h mpcqp_predict; com_traj = Sx x0 + Su U,
+        mpc.py:293-294), for B robots in one launch.
+
+        state, xref, contact_schedule, feet, robot: as for ``solve``.  U: [B,N,12] or [B,12N],
+        usually ``solve(..., return_all=True).U``; every entry is used as given.  Returns a
+        PredictResult (device tensors)."""
+        st = torch.as_tensor(state)
+        B = int(st.shape[0]) if st.dim() == 2 else 1
+        N = self.horizon
+        cur = torch.cuda.current_stream(self.device)
+        if stream is None:
+            stream = cur
+        elif stream != cur:
+            stream.wait_stream(cur)   # as solve: inputs made on the current stream must be ready
+        with torch.cuda.stream(stream):
+            x0 = self._dev(state, (B, 13), "state")
+            xr = self._dev(xref, (B, N, 13), "xref")
+            ct = self._dev(contact_schedule, (B, N, 4), "contact_schedule")
+            ft = self._dev(feet, (B, 4, 3), "feet")
+            Ut = self._dev(U, (B, N, 12), "U")
+            if robot is None or isinstance(robot, str) or hasattr(robot, "mass_base"):
+                rec = self.default_robot if robot is None else self._robot_record(robot)
+                if rec is None:
+                    raise ValueError("no robot parameters")
+                rb = torch.as_tensor(np.tile(rec, (B, 1)))
+            else:
+                rt = torch.as_tensor(robot)
+                rb = rt.reshape(1, -1).expand(B, -1) if rt.dim() == 1 else rt
+            rb = self._dev(rb, (B, ROBOT_STRIDE), "robot")
+            X = torch.empty((B, N, 13), dtype=torch.float32, device=self.device)
+            report = torch.empty((B, _lib.PREDICT_REPORT), dtype=torch.float64, device=self.device)
+            status = torch.empty((B,), dtype=torch.int32, device=self.device)
+            self.predict_raw(B, x0, xr, ct, ft, rb, Ut, X, report, status, stream=stream)
+            for t in (x0, xr, ct, ft, rb, Ut, X, report, status):
+                if t.numel():
+                    t.record_stream(stream)
+        return PredictResult(X, report, status)
+
+    def _predict_args(self, B, x0, xref, contact, feet, robot, U, X, report, status):
+        """The argument tuple of mpcqp_predict after the checks every caller shares: contiguous
+        tensors of the right dtype and size on the engine's device (the kernel reads and writes B
+        rows of each); X, report and status may be None."""
+        B, N = int(B), self.horizon
+        f32 = torch.float32
+        for name, t, shape, dtype, need in (
+                ("x0", x0, (B, 13), f32, True), ("xref", xref, (B, N, 13), f32, True),
+                ("contact", contact, (B, N, 4), f32, True), ("feet", feet, (B, 4, 3), f32, True),
+                ("robot", robot, (B, ROBOT_STRIDE), f32, True), ("U", U, (B, N, 12), f32, True),
+                ("X", X, (B, N, 13), f32, False), ("report", report, (B, _lib.PREDICT_REPORT), torch.float64, False),
+                ("status", status, (B,), torch.int32, False)):
+            if t is None:
+                if need:
+                    raise ValueError(f"predict: {name} is required")
+                continue
+            if not (t.dtype == dtype and t.is_contiguous() and t.device == self.device
+                    and t.numel() == int(np.prod(shape))):
+                raise ValueError(f"predict: {name} must be a contiguous {dtype} tensor of shape {list(shape)} on "
+                                 f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return (self._ctx, B, 0, _ptr(x0), _ptr(xref), _ptr(contact), _ptr(feet), _ptr(robot), _ptr(U), _ptr(X),
+                _ptr(report), _ptr(status))
+
+    def predict_raw(self, B, x0, xref, contact, feet, robot, U, X=None, report=None, status=None, stream=None):
+        """mpcqp_predict on preallocated contiguous device tensors (float32; report [B,PREDICT_REPORT]
+        float64, status [B] int32): one launch on ``stream`` (default: the current stream), no
+        allocation or synchronisation.  X, report and status are each optional; a tensor of the
+        wrong dtype, size or device raises ValueError."""
+        args = self._predict_args(B, x0, xref, contact, feet, robot, U, X, report, status)
+        _lib.check(self._ctx, self.lib.mpcqp_predict(*args, self._stream_ptr(stream)), "mpcqp_predict")
+
+    def bind_predict(self, B, x0, xref, contact, feet, robot, U, X=None, report=None, status=None):
+        """predict_raw with its checks made and its device pointers resolved once: returns
+        ``launch(stream)`` (see bind_solve), e.g. for capture into a HIP graph."""
+        lib, ctx = self.lib, self._ctx
+        args = self._predict_args(B, x0, xref, contact, feet, robot, U, X, report, status)
+        keep = (x0, xref, contact, feet, robot, U, X, report, status)   # the pointers' owners stay alive
+
+        def launch(stream):
+            _lib.check(ctx, lib.mpcqp_predict(*args, ctypes.c_void_p(stream.cuda_stream)), "mpcqp_predict")
         launch.buffers = keep
         return launch
 
