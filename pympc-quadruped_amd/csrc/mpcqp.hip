@@ -38,6 +38,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_predict_abi.h"
+#include "mpcqp_plant_abi.h"
 
 namespace {
 
@@ -358,6 +359,7 @@ constexpr int kPrioTab = 4096;
 #include "mpcqp_attitude.h"
 #include "mpcqp_terrain.h"
 #include "mpcqp_predict.h"
+#include "mpcqp_plant.h"
 // the kernel headers' constants are those of include/mpcqp.h
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 static_assert(EST_STRIDE == MPCQP_EST_STRIDE, "estimator record stride");
@@ -719,6 +721,12 @@ struct mpcqp_ctx {
   TerParams ter;      // terrain-plane constants (mpcqp_set_terrain)
   const float* ground;   // the swing leg's ground planes (caller-owned device buffer), mpcqp_set_ground
   int ground_cap;
+  // plant constants (mpcqp_set_plant); ground_z follows the swing's touchdown_z until it is set
+  double plant_foot_mass;
+  int plant_substeps;
+  double plant_ground_z;
+  bool plant_ground_set;
+  double plant_contact_tol;
   std::string err;
 };
 
@@ -923,6 +931,11 @@ int mpcqp_create(const mpcqp_params* p, int32_t device, mpcqp_ctx** out) {
   ctx->ter = TerParams{0.5, 1e-3, 0.5, 1.0, 0};
   ctx->ground = nullptr;
   ctx->ground_cap = 0;
+  ctx->plant_foot_mass = 0.15;
+  ctx->plant_substeps = 1;
+  ctx->plant_ground_z = 0.0;
+  ctx->plant_ground_set = false;
+  ctx->plant_contact_tol = 1e-4;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->ncu = prop.multiProcessorCount;
   if (ctx->ncu <= 0) ctx->ncu = 256;
@@ -1611,6 +1624,68 @@ int mpcqp_predict(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0,
   if (kp.N <= 16) full ? launch(mpcqp_predict_kernel<16, true>) : launch(mpcqp_predict_kernel<16, false>);
   else full ? launch(mpcqp_predict_kernel<kMaxN, true>) : launch(mpcqp_predict_kernel<kMaxN, false>);
   return launched(ctx, "predict launch");
+}
+
+// ---- the rigid-body plant (mpcqp_plant.h): the stage the reference's scripts hand to a simulator
+// (gym.simulate, sim.step()), as a single rigid body on massless legs.  An invalid constant leaves
+// the previous set in force.
+int mpcqp_set_plant(mpcqp_ctx* ctx, double foot_mass, int32_t substeps, double ground_z, double contact_tol) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (!all_finite({foot_mass, ground_z, contact_tol})) return set_err(ctx, MPCQP_ERR_ARG, "non-finite plant constant");
+  if (!(foot_mass > 0.0)) return set_err(ctx, MPCQP_ERR_ARG, "plant: foot_mass <= 0");
+  if (substeps < 1 || substeps > MPCQP_PLANT_MAX_SUBSTEPS)
+    return set_err(ctx, MPCQP_ERR_ARG, "plant: substeps outside 1..16");
+  ctx->plant_foot_mass = foot_mass;
+  ctx->plant_substeps = substeps;
+  ctx->plant_ground_z = ground_z;
+  ctx->plant_ground_set = true;
+  ctx->plant_contact_tol = contact_tol;
+  return MPCQP_OK;
+}
+
+static PlantParams plant_params(const mpcqp_ctx* ctx) {
+  PlantParams pp;
+  pp.dt_control = ctx->dt_control;
+  pp.gravity = ctx->gravity;
+  pp.foot_mass = ctx->plant_foot_mass;
+  pp.ground_z = ctx->plant_ground_set ? ctx->plant_ground_z : ctx->touchdown_z;
+  pp.contact_tol = ctx->plant_contact_tol;
+  pp.substeps = ctx->plant_substeps;
+  return pp;
+}
+
+int mpcqp_plant(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* tau, const float* robot, const double* geom,
+                const float* plane, double* plant_state, float* root_states, float* dof_states, float* gyro,
+                float* accel, float* touch, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown plant flags");
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "plant: batch < 0");
+  if (!tau || !robot || !geom || !plant_state || !root_states || !dof_states)
+    return set_err(ctx, MPCQP_ERR_ARG, "null plant input/state/output pointer");
+  if (int rc = aligned16(ctx, plant_state, "plant_state")) return rc;
+  if ((uintptr_t)dof_states & 7) return set_err(ctx, MPCQP_ERR_ARG, "plant: dof_states is not 8-byte aligned");
+  if (batch == 0) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  hipLaunchKernelGGL(mpcqp_plant_kernel, dim3((batch + kPlantRobots - 1) / kPlantRobots), dim3(kPlantThreads), 0,
+                     (hipStream_t)stream, plant_params(ctx), (int)batch, tau, robot, geom, plane, plant_state,
+                     root_states, dof_states, gyro, accel, touch, status);
+  return launched(ctx, "plant launch");
+}
+
+int mpcqp_plant_reset(mpcqp_ctx* ctx, int32_t batch, const float* root_states, const float* dof_states,
+                      const double* geom, const float* plane, double* plant_state, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "plant reset: batch < 0");
+  if (!root_states || !dof_states || !geom || !plant_state)
+    return set_err(ctx, MPCQP_ERR_ARG, "null plant reset input/state pointer");
+  if (int rc = aligned16(ctx, plant_state, "plant_state")) return rc;
+  if (batch == 0) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  hipLaunchKernelGGL(mpcqp_plant_reset_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                     plant_params(ctx), (int)batch, root_states, dof_states, geom, plane, plant_state);
+  return launched(ctx, "plant reset launch");
 }
 
 int mpcqp_destroy(mpcqp_ctx* ctx) {

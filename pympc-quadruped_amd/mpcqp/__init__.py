@@ -6,7 +6,7 @@ Drop-in for the formulate-and-solve hot path of yinghansun/pympc-quadruped
 from .params import (DT_MPC, GAITS, GRAVITY, LEG_GEOMETRY, MU, Q_DIAG, R_DIAG, ROBOT_PRESETS, ROBOT_STRIDE,
                      leg_geometry_from_urdf, pack_leg_geometry, pack_robot, robot_from_config)
 
-__all__ = ["LinearMpc", "SolveResult", "PredictResult", "BatchedTerrain", "DT_MPC", "GAITS", "GRAVITY", "LEG_GEOMETRY", "MU", "Q_DIAG", "R_DIAG",
+__all__ = ["LinearMpc", "SolveResult", "PredictResult", "BatchedTerrain", "BatchedPlant", "DT_MPC", "GAITS", "GRAVITY", "LEG_GEOMETRY", "MU", "Q_DIAG", "R_DIAG",
            "ROBOT_PRESETS", "ROBOT_STRIDE", "leg_geometry_from_urdf", "pack_leg_geometry", "pack_robot",
            "robot_from_config"]
 
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "BatchedTerrain":
         from .terrain import BatchedTerrain
         return BatchedTerrain
+    if name == "BatchedPlant":
+        from .plant import BatchedPlant
+        return BatchedPlant
     raise AttributeError(name)

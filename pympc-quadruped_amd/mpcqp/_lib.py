@@ -39,6 +39,8 @@ ATT_STRIDE = 8      # MPCQP_ATT_STRIDE: float64 orientation record per robot (q[
 TERRAIN_STRIDE = 20        # MPCQP_TERRAIN_STRIDE: float64 terrain record per robot (history[4][3], initialised, n[3], d, fitted)
 TERRAIN_SWING_STATE = 1    # MPCQP_TERRAIN_SWING_STATE: contact is a swing_state, stance where !(value > 0)
 TERRAIN_ROOT_STATES = 2    # MPCQP_TERRAIN_ROOT_STATES: quat is a root-state tensor [B,13]
+PLANT_STRIDE = 48          # MPCQP_PLANT_STRIDE (mpcqp_plant_abi.h): float64 plant record per robot (pos, quat, vel, omega, feet, foot velocities, contact, flag word, call count)
+PLANT_MAX_SUBSTEPS = 16    # MPCQP_PLANT_MAX_SUBSTEPS (mpcqp_plant_abi.h)
 PREDICT_REPORT = 4         # MPCQP_PREDICT_REPORT (mpcqp_predict_abi.h): float64 report per robot (cost, cost_free, cone margin, swing residual)
 
 
@@ -95,6 +97,13 @@ EXPORTED_SYMBOLS = tuple(SIGNATURES)   # every symbol declared in include/mpcqp.
 PREDICT_SIGNATURES = {
     "mpcqp_predict": (_int, [_vp, _i32, _i32] + [_vp] * 10),
 }
+# The companion header include/mpcqp_plant_abi.h, one row per function it declares
+# (tests/test_plant.py holds each row to its declaration, position by position).
+PLANT_SIGNATURES = {
+    "mpcqp_plant": (_int, [_vp, _i32, _i32] + [_vp] * 12),
+    "mpcqp_plant_reset": (_int, [_vp, _i32] + [_vp] * 6),
+    "mpcqp_set_plant": (_int, [_vp, _f64, _i32, _f64, _f64]),
+}
 
 
 class MpcqpError(RuntimeError):
@@ -113,7 +122,7 @@ def load():
         raise MpcqpError(f"{LIB_PATH} not built: run __graft_entry__.build() "
                          "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **PREDICT_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **PREDICT_SIGNATURES, **PLANT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mpcqp_abi_version() != ABI_VERSION:

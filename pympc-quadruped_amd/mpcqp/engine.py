@@ -445,6 +445,7 @@ class LinearMpc:
                                         kd.ctypes.data if kd is not None else None, float(touchdown_z),
                                         float(vel_gain))
         _lib.check(self._ctx, code, "mpcqp_set_swing")
+        self.touchdown_z = float(touchdown_z)   # the plant's level ground follows it until it is given one
 
     def leg_torques(self, tick, iterations_between_mpc, vel_body_des, yaw_rate_des, gait, thighs, pos_feet,
                     foot_pos_base, foot_vel_base, jac, u0, swing_mem, tau, quat=None, pos=None, vel=None, rot=None,

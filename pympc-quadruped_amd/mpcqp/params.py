@@ -49,6 +49,7 @@ HIP_OFFSETS = {"a1": (0.183, 0.047 + 0.08505), "aliengo": (0.2399, 0.051 + 0.083
 # mirror it (x sign + + - -, y sign + - + - for FL, FR, RL, RR)
 LEG_GEOMETRY = {"a1": (0.183, 0.047, 0.08505, 0.2, 0.2), "aliengo": (0.2399, 0.051, 0.083, 0.25, 0.25)}
 KIN_STRIDE = 8      # MPCQP_KIN_STRIDE: float64 geometry record per robot
+PLANT_STRIDE = 48   # MPCQP_PLANT_STRIDE: float64 plant record per robot (mpcqp_plant_abi.h)
 LEG_NAMES = ("FL", "FR", "RL", "RR")
 LEG_SIGNS = ((1.0, 1.0), (1.0, -1.0), (-1.0, 1.0), (-1.0, -1.0))
 
