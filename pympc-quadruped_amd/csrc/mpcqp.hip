@@ -39,6 +39,7 @@
 #include "mpcqp.h"
 #include "mpcqp_predict_abi.h"
 #include "mpcqp_plant_abi.h"
+#include "mpcqp_certify_abi.h"
 
 namespace {
 
@@ -359,6 +360,7 @@ constexpr int kPrioTab = 4096;
 #include "mpcqp_attitude.h"
 #include "mpcqp_terrain.h"
 #include "mpcqp_predict.h"
+#include "mpcqp_certify.h"
 #include "mpcqp_plant.h"
 // the kernel headers' constants are those of include/mpcqp.h
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
@@ -1593,6 +1595,21 @@ int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos
   return launched(ctx, "terrain launch");
 }
 
+// What the kernels that evaluate a given U (mpcqp_predict, mpcqp_certify) take from the context:
+// the horizon, dt and the weights; nothing of the solve.
+static KParams eval_params(const mpcqp_ctx* ctx) {
+  KParams kp;
+  kp.N = ctx->params.horizon;
+  kp.max_iter = 0;
+  kp.dt = ctx->params.dt;
+  for (int i = 0; i < NX; ++i) kp.q[i] = ctx->params.q_diag[i];
+  for (int i = 0; i < NU; ++i) kp.r[i] = ctx->params.r_diag[i];
+  kp.wfull = ctx->wdev;
+  kp.warm = nullptr;
+  kp.warm_cap = 0;
+  return kp;
+}
+
 // The trajectory the QP believes a force sequence produces (com_traj = Sx x0 + Su U,
 // mpc.py:293-294), its cost, cone margin and swing residual: one launch, one wavefront per robot.
 int mpcqp_predict(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0, const float* xref,
@@ -1606,15 +1623,7 @@ int mpcqp_predict(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0,
   if (batch == 0 || (!X && !report && !status)) return MPCQP_OK;
   DeviceScope dev(ctx->device);
   if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
-  KParams kp;
-  kp.N = ctx->params.horizon;
-  kp.max_iter = 0;
-  kp.dt = ctx->params.dt;
-  for (int i = 0; i < NX; ++i) kp.q[i] = ctx->params.q_diag[i];
-  for (int i = 0; i < NU; ++i) kp.r[i] = ctx->params.r_diag[i];
-  kp.wfull = ctx->wdev;
-  kp.warm = nullptr;
-  kp.warm_cap = 0;
+  const KParams kp = eval_params(ctx);
   const bool full = kp.wfull != nullptr;
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(batch), dim3(LANES), 0, (hipStream_t)stream, kp, (int)batch, x0, xref, contact, feet,
@@ -1624,6 +1633,31 @@ int mpcqp_predict(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0,
   if (kp.N <= 16) full ? launch(mpcqp_predict_kernel<16, true>) : launch(mpcqp_predict_kernel<16, false>);
   else full ? launch(mpcqp_predict_kernel<kMaxN, true>) : launch(mpcqp_predict_kernel<kMaxN, false>);
   return launched(ctx, "predict launch");
+}
+
+// The gradient of the QP's objective at a force sequence, the objective and the duality gap the
+// friction pyramids give in closed form (mpcqp_certify.h): one launch, one wavefront per robot.
+int mpcqp_certify(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0, const float* xref,
+                  const float* contact, const float* feet, const float* robot, const float* U, float* G,
+                  double* report, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown certify flags");
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "certify: batch < 0");
+  if (!x0 || !xref || !contact || !feet || !robot || !U)
+    return set_err(ctx, MPCQP_ERR_ARG, "null certify input pointer");
+  if (batch == 0 || (!G && !report && !status)) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  const KParams kp = eval_params(ctx);
+  const bool full = kp.wfull != nullptr;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(LANES), 0, (hipStream_t)stream, kp, (int)batch, x0, xref, contact, feet,
+                       robot, U, G, report, status);
+  };
+  // the instantiation whose LDS holds this horizon and these weights
+  if (kp.N <= 16) full ? launch(mpcqp_certify_kernel<16, true>) : launch(mpcqp_certify_kernel<16, false>);
+  else full ? launch(mpcqp_certify_kernel<kMaxN, true>) : launch(mpcqp_certify_kernel<kMaxN, false>);
+  return launched(ctx, "certify launch");
 }
 
 // ---- the rigid-body plant (mpcqp_plant.h): the stage the reference's scripts hand to a simulator

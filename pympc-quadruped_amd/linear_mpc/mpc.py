@@ -294,6 +294,30 @@ class ModelPredictiveController():
             raise RuntimeError("mpcqp: predicted trajectory is not finite")
         return out
 
+    def optimality_gap(self):
+        """(objective, gap) of the last MPC tick's U as Python floats: the QP's objective
+        1/2 U^T H U + g^T U and a bound on how far it lies above the optimum, computed on the
+        device (mpcqp_certify) from the buffers that tick left, as predicted_trajectory does.  For
+        the feasible U a solve returns, 0 <= objective - optimum <= gap; the gap is a first-order
+        bound, tight at the optimum and loose far from it.  Raises RuntimeError before the first
+        MPC tick."""
+        import torch
+        if self._engine is None or not self._solve_fns or self._up_views is None:
+            raise RuntimeError("optimality_gap: no MPC tick has run yet")
+        e, dv, up = self._engine, self._dev, self._up_views
+        N = self.horizon
+        rep = dv.get("report_cert")
+        if rep is None:
+            rep = dv["report_cert"] = torch.zeros((1, 4), dtype=torch.float64, device=e.device)
+            dv["status_cert"] = torch.zeros((1,), dtype=torch.int32, device=e.device)
+            self._certify_fn = e.bind_certify(1, dv["x0"], dv["xref"], up["contact"].reshape(1, N, 4), up["feet"],
+                                              dv["robot"], dv["U"].reshape(1, N, 12), None, rep, dv["status_cert"])
+        self._certify_fn(torch.cuda.current_stream(e.device))
+        out = rep.cpu().numpy()[0]
+        if int(dv["status_cert"].cpu()[0]) != 0:
+            raise RuntimeError("mpcqp: optimality gap is not finite")
+        return float(out[0]), float(out[1])
+
     def generate_reference_trajectory(self, vel_base_des, yaw_turn_rate):
         """mpc.py:110-170 alone (stateful clamp + roll/pitch compensation), on the device.
 

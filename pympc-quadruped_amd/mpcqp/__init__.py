@@ -6,14 +6,14 @@ Drop-in for the formulate-and-solve hot path of yinghansun/pympc-quadruped
 from .params import (DT_MPC, GAITS, GRAVITY, LEG_GEOMETRY, MU, Q_DIAG, R_DIAG, ROBOT_PRESETS, ROBOT_STRIDE,
                      leg_geometry_from_urdf, pack_leg_geometry, pack_robot, robot_from_config)
 
-__all__ = ["LinearMpc", "SolveResult", "PredictResult", "BatchedTerrain", "BatchedPlant", "DT_MPC", "GAITS", "GRAVITY", "LEG_GEOMETRY", "MU", "Q_DIAG", "R_DIAG",
+__all__ = ["LinearMpc", "SolveResult", "PredictResult", "CertifyResult", "BatchedTerrain", "BatchedPlant", "DT_MPC", "GAITS", "GRAVITY", "LEG_GEOMETRY", "MU", "Q_DIAG", "R_DIAG",
            "ROBOT_PRESETS", "ROBOT_STRIDE", "leg_geometry_from_urdf", "pack_leg_geometry", "pack_robot",
            "robot_from_config"]
 
 
 def __getattr__(name):
     # torch is imported lazily so that the host-only helpers stay importable without it
-    if name in ("LinearMpc", "SolveResult", "PredictResult"):
+    if name in ("LinearMpc", "SolveResult", "PredictResult", "CertifyResult"):
         from . import engine
         return getattr(engine, name)
     if name == "BatchedTerrain":

@@ -43,6 +43,8 @@ PLANT_STRIDE = 48          # MPCQP_PLANT_STRIDE (mpcqp_plant_abi.h): float64 pla
 PLANT_MAX_SUBSTEPS = 16    # MPCQP_PLANT_MAX_SUBSTEPS (mpcqp_plant_abi.h)
 PREDICT_REPORT = 4         # MPCQP_PREDICT_REPORT (mpcqp_predict_abi.h): float64 report per robot (cost, cost_free, cone margin, swing residual)
 
+CERTIFY_REPORT = 4         # MPCQP_CERTIFY_REPORT (mpcqp_certify_abi.h): float64 report per robot (objective, gap, lower bound, worst foot-step term)
+
 
 class MpcqpParams(ctypes.Structure):
     """struct mpcqp_params (include/mpcqp.h)."""
@@ -104,6 +106,11 @@ PLANT_SIGNATURES = {
     "mpcqp_plant_reset": (_int, [_vp, _i32] + [_vp] * 6),
     "mpcqp_set_plant": (_int, [_vp, _f64, _i32, _f64, _f64]),
 }
+# The companion header include/mpcqp_certify_abi.h, one row per function it declares
+# (tests/test_certify.py holds the row to its declaration, position by position).
+CERTIFY_SIGNATURES = {
+    "mpcqp_certify": (_int, [_vp, _i32, _i32] + [_vp] * 10),
+}
 
 
 class MpcqpError(RuntimeError):
@@ -122,7 +129,8 @@ def load():
         raise MpcqpError(f"{LIB_PATH} not built: run __graft_entry__.build() "
                          "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **PREDICT_SIGNATURES, **PLANT_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **PREDICT_SIGNATURES, **PLANT_SIGNATURES,
+                                       **CERTIFY_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mpcqp_abi_version() != ABI_VERSION:

@@ -59,6 +59,21 @@ class PredictResult:
         self.cone_margin, self.swing_residual = report[:, 2], report[:, 3]
 
 
+class CertifyResult:
+    """What ``LinearMpc.certify`` returns (include/mpcqp_certify_abi.h mpcqp_certify), device
+    tensors: G [B,N,12] float32, the gradient H U + g of the QP's objective phi at U; objective,
+    gap, lower and worst [B] float64, views of the one ``report`` tensor [B,CERTIFY_REPORT];
+    status [B] int32 (STATUS_OK or STATUS_NONFINITE, whose G and report are zeros).
+    ``lower = objective - gap`` never exceeds the optimum phi*; for a feasible U
+    ``objective - phi* <= gap``.  The gap is a first-order bound: tight at the optimum and loose
+    far from it."""
+
+    def __init__(self, G, report, status):
+        self.G, self.report, self.status = G, report, status
+        self.objective, self.gap = report[:, 0], report[:, 1]
+        self.lower, self.worst = report[:, 2], report[:, 3]
+
+
 class LinearMpc:
     """Batched reference MPC: one QP per robot, solved on one MI355X.
 
@@ -287,6 +302,12 @@ class LinearMpc:
         state, xref, contact_schedule, feet, robot: as for ``solve``.  U: [B,N,12] or [B,12N],
         usually ``solve(..., return_all=True).U``; every entry is used as given.  Returns a
         PredictResult (device tensors)."""
+        return PredictResult(*self._evaluate(self.predict_raw, 13, _lib.PREDICT_REPORT, state, xref, contact_schedule,
+                                             feet, U, robot, stream))
+
+    def _evaluate(self, raw, out_cols, report_words, state, xref, contact_schedule, feet, U, robot, stream):
+        """What predict and certify share: the inputs brought to the device, the three outputs
+        allocated ([B,N,out_cols] float32, the report, the status) and ``raw`` launched on them."""
         st = torch.as_tensor(state)
         B = int(st.shape[0]) if st.dim() == 2 else 1
         N = self.horizon
@@ -310,37 +331,43 @@ class LinearMpc:
                 rt = torch.as_tensor(robot)
                 rb = rt.reshape(1, -1).expand(B, -1) if rt.dim() == 1 else rt
             rb = self._dev(rb, (B, ROBOT_STRIDE), "robot")
-            X = torch.empty((B, N, 13), dtype=torch.float32, device=self.device)
-            report = torch.empty((B, _lib.PREDICT_REPORT), dtype=torch.float64, device=self.device)
+            out = torch.empty((B, N, out_cols), dtype=torch.float32, device=self.device)
+            report = torch.empty((B, report_words), dtype=torch.float64, device=self.device)
             status = torch.empty((B,), dtype=torch.int32, device=self.device)
-            self.predict_raw(B, x0, xr, ct, ft, rb, Ut, X, report, status, stream=stream)
-            for t in (x0, xr, ct, ft, rb, Ut, X, report, status):
+            raw(B, x0, xr, ct, ft, rb, Ut, out, report, status, stream=stream)
+            for t in (x0, xr, ct, ft, rb, Ut, out, report, status):
                 if t.numel():
                     t.record_stream(stream)
-        return PredictResult(X, report, status)
+        return out, report, status
 
-    def _predict_args(self, B, x0, xref, contact, feet, robot, U, X, report, status):
-        """The argument tuple of mpcqp_predict after the checks every caller shares: contiguous
-        tensors of the right dtype and size on the engine's device (the kernel reads and writes B
-        rows of each); X, report and status may be None."""
+    def _eval_args(self, call, B, x0, xref, contact, feet, robot, U, out_name, out, out_cols, report, report_words,
+                   status):
+        """The argument tuple of mpcqp_predict / mpcqp_certify after the checks every caller
+        shares: contiguous tensors of the right dtype and size on the engine's device (the kernel
+        reads and writes B rows of each); the three outputs may be None."""
         B, N = int(B), self.horizon
         f32 = torch.float32
         for name, t, shape, dtype, need in (
                 ("x0", x0, (B, 13), f32, True), ("xref", xref, (B, N, 13), f32, True),
                 ("contact", contact, (B, N, 4), f32, True), ("feet", feet, (B, 4, 3), f32, True),
                 ("robot", robot, (B, ROBOT_STRIDE), f32, True), ("U", U, (B, N, 12), f32, True),
-                ("X", X, (B, N, 13), f32, False), ("report", report, (B, _lib.PREDICT_REPORT), torch.float64, False),
+                (out_name, out, (B, N, out_cols), f32, False), ("report", report, (B, report_words), torch.float64, False),
                 ("status", status, (B,), torch.int32, False)):
             if t is None:
                 if need:
-                    raise ValueError(f"predict: {name} is required")
+                    raise ValueError(f"{call}: {name} is required")
                 continue
             if not (t.dtype == dtype and t.is_contiguous() and t.device == self.device
                     and t.numel() == int(np.prod(shape))):
-                raise ValueError(f"predict: {name} must be a contiguous {dtype} tensor of shape {list(shape)} on "
+                raise ValueError(f"{call}: {name} must be a contiguous {dtype} tensor of shape {list(shape)} on "
                                  f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return (self._ctx, B, 0, _ptr(x0), _ptr(xref), _ptr(contact), _ptr(feet), _ptr(robot), _ptr(U), _ptr(X),
+        return (self._ctx, B, 0, _ptr(x0), _ptr(xref), _ptr(contact), _ptr(feet), _ptr(robot), _ptr(U), _ptr(out),
                 _ptr(report), _ptr(status))
+
+    def _predict_args(self, B, x0, xref, contact, feet, robot, U, X, report, status):
+        """The argument tuple of mpcqp_predict after the checks every caller shares."""
+        return self._eval_args("predict", B, x0, xref, contact, feet, robot, U, "X", X, 13, report,
+                               _lib.PREDICT_REPORT, status)
 
     def predict_raw(self, B, x0, xref, contact, feet, robot, U, X=None, report=None, status=None, stream=None):
         """mpcqp_predict on preallocated contiguous device tensors (float32; report [B,PREDICT_REPORT]
@@ -359,6 +386,43 @@ class LinearMpc:
 
         def launch(stream):
             _lib.check(ctx, lib.mpcqp_predict(*args, ctypes.c_void_p(stream.cuda_stream)), "mpcqp_predict")
+        launch.buffers = keep
+        return launch
+
+    def certify(self, state, xref, contact_schedule, feet, U, robot=None, stream=None):
+        """How far the force sequence ``U`` is from the QP's optimum (include/mpcqp_certify_abi.h
+        mpcqp_certify), for B robots in one launch: the gradient G = H U + g of the objective
+        phi(U) = cost - cost_free, phi(U) itself, and the duality gap the friction pyramids give in
+        closed form, with ``lower = objective - gap <= phi*`` for any finite U and
+        ``0 <= phi(U) - phi* <= gap`` for a feasible one.  The gap is a first-order bound: tight
+        at the optimum and loose far from it.
+
+        Arguments as for ``predict``.  Returns a CertifyResult (device tensors)."""
+        return CertifyResult(*self._evaluate(self.certify_raw, 12, _lib.CERTIFY_REPORT, state, xref, contact_schedule,
+                                             feet, U, robot, stream))
+
+    def _certify_args(self, B, x0, xref, contact, feet, robot, U, G, report, status):
+        """The argument tuple of mpcqp_certify after the checks every caller shares."""
+        return self._eval_args("certify", B, x0, xref, contact, feet, robot, U, "G", G, 12, report,
+                               _lib.CERTIFY_REPORT, status)
+
+    def certify_raw(self, B, x0, xref, contact, feet, robot, U, G=None, report=None, status=None, stream=None):
+        """mpcqp_certify on preallocated contiguous device tensors (float32; G [B,N,12]; report
+        [B,CERTIFY_REPORT] float64, status [B] int32): one launch on ``stream`` (default: the
+        current stream), no allocation or synchronisation.  G, report and status are each
+        optional; a tensor of the wrong dtype, size or device raises ValueError."""
+        args = self._certify_args(B, x0, xref, contact, feet, robot, U, G, report, status)
+        _lib.check(self._ctx, self.lib.mpcqp_certify(*args, self._stream_ptr(stream)), "mpcqp_certify")
+
+    def bind_certify(self, B, x0, xref, contact, feet, robot, U, G=None, report=None, status=None):
+        """certify_raw with its checks made and its device pointers resolved once: returns
+        ``launch(stream)`` (see bind_solve), e.g. for capture into a HIP graph."""
+        lib, ctx = self.lib, self._ctx
+        args = self._certify_args(B, x0, xref, contact, feet, robot, U, G, report, status)
+        keep = (x0, xref, contact, feet, robot, U, G, report, status)   # the pointers' owners stay alive
+
+        def launch(stream):
+            _lib.check(ctx, lib.mpcqp_certify(*args, ctypes.c_void_p(stream.cuda_stream)), "mpcqp_certify")
         launch.buffers = keep
         return launch
 
