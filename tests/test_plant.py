@@ -209,6 +209,131 @@ def test_header_matches_the_restatement_on_single_ticks(header, substeps, tilted
     assert (got_rec[:, pr.FLAGS] == 0).all() and np.array_equal(got_rec[:, pr.TICK], st["rec"][:, pr.TICK] + 1)
 
 
+def check_set(st, par, trace, ref):
+    """What a seeded set promises, from the restatement alone (shared with
+    tests/test_gpu_plant_edges.py): every case occurs and does what its name says in at least
+    90 % of its legs, the flag words are the set's, the slow set turns slowly."""
+    case = st["case"]
+    after = ref[:, pr.CONTACT:pr.CONTACT + 4] != 0
+    land = np.any([t["land"] for t in trace], 0)
+    share = {"stance": after[case == 0].mean(), "friction clamp": (trace[0]["over"] & after)[case == 1].mean(),
+             "release": trace[0]["release"][case == 2].mean(), "swing": (~trace[0]["pinned"])[case == 3].mean(),
+             "touchdown": land[case == 4].mean()}
+    if "still" not in st:                            # the slow set leaves most robots one case
+        assert all((case == k).sum() >= 4 for k in range(len(pr.CASES)))
+        assert min(share.values()) >= 0.9, share
+        assert not trace[0]["over"][case == 0].any()
+    assert np.array_equal(ref[:, pr.FLAGS], st["word"] if "word" in st else np.zeros(len(ref)))
+    if "still" in st:
+        t = np.stack([x["t"] for x in trace])
+        assert (t < 1e-6).all(0).mean() > 0.5 and (t[:, st["zero"]] == 0.0).all() and st["zero"].any()
+        assert (t[:, st["still"]] < 1e-15).all()
+        assert ((t > 0.0) & (t < 1e-6)).all(0).mean() > 0.25           # the small branch with a turn that is not zero
+        assert (t >= 1e-6).all(0).mean() > 0.1                          # and the large one
+        assert np.abs(t / 1e-6 - 1.0).min() > 1e-6                     # no robot on the branch point itself
+        kept = ref[:, pr.QUAT:pr.QUAT + 4].view(np.uint64) == st["rec"][:, pr.QUAT:pr.QUAT + 4].view(np.uint64)
+        assert kept[st["zero"]].all()
+    return share
+
+
+SETS = {"mixed": (pr.make_mixed_states, 22), "clamped": (pr.make_clamped_states, 31), "slow": (pr.make_slow_states, 40)}
+
+
+@pytest.mark.parametrize("substeps", [1, 16])
+@pytest.mark.parametrize("name", sorted(SETS))
+def test_header_matches_the_restatement_on_the_edge_sets(header, name, substeps):
+    """The sets of tests/test_gpu_plant_edges.py through the host-compiled header: a mixed fleet
+    (A1 and Aliengo in turn, own mass, mu, inertia) on per-robot slopes, legs at every clamp of
+    the inverse kinematics, rotations in the small branch of plant_quat_step; substeps 1 and 16,
+    the ABI's maximum.  Measured here, the record norm-wise per robot at substeps 1 / 16: mixed
+    8.5e-16 / 3.1e-15, clamped 6.6e-16 / 3.3e-15, slow 7.5e-16 / 6.8e-16; every float32 output
+    within one ulp, flag words equal, no robot within 1e-9 of a threshold."""
+    B = 512
+    make, seed = SETS[name]
+    par = pr.Params(substeps=substeps)
+    st = make(B, seed, par)
+    plane = st.get("plane")
+    args = (st["tau"], st["robot"], st["geom"], par, plane)
+    near = pr.near_threshold(st["rec"], *args)
+    assert near.mean() <= 0.02
+    ref = st["rec"].copy()
+    want = pr.plant_step(ref, *args)
+    share = check_set(st, par, pr.trace_step(st["rec"], *args), ref)
+    got_rec = st["rec"].copy()
+    got = run_header(header, got_rec, *args)
+    keep = ~near
+    cl = st.get("clamped", np.zeros((B, 4), bool))
+    # a clamped leg's foot falls freely and is compared; its hip and thigh angles and its joint
+    # rates hang on rounding noise (J_b^-1 near 1e14) and are not
+    err = pr.record_error(got_rec, ref)[keep]
+    print(f"\n{name}, substeps {substeps}: {near.mean():.4f} near a threshold, cases {share}\n"
+          f"record, norm-wise per robot: worst {err.max():.2e} (bound {CPU_BOUND:g})")
+    assert err.max() <= CPU_BOUND
+    assert np.array_equal(got_rec[keep, pr.CONTACT:pr.WORDS], ref[keep, pr.CONTACT:pr.WORDS])    # contact, flag word, count
+    assert np.array_equal(got_rec[:, pr.FLAGS], ref[:, pr.FLAGS])
+    assert np.array_equal(got["status"], want["status"]) and (want["status"] == 0).all()
+    for out in (got, want):
+        assert all(np.isfinite(out[k]).all() for k in ("root", "dofs", "gyro", "accel")) and np.isfinite(got_rec).all()
+        knee = -out["dofs"].reshape(B, 4, 3, 2)[:, :, 2, 0].astype(np.float64)[cl & (st.get("kind") == 0)]
+        assert (knee > 0).all() and (knee <= np.sqrt(2 * pr.IK_EPS) * (1 + 1e-6)).all()       # stretched: at its clamp
+        fold = np.pi + out["dofs"].reshape(B, 4, 3, 2)[:, :, 2, 0].astype(np.float64)[cl & (st.get("kind") == 1)]
+        assert (np.abs(fold) <= 2.0 ** -22).all()                                             # folded: -pi, in float32
+    moving = ~st.get("still", np.zeros(B, bool))          # a robot at rest: its gyro is rounding noise, 1e-19
+    assert np.abs(got["gyro"][~moving]).max(initial=0.0) <= 1e-15 and np.abs(want["gyro"][~moving]).max(initial=0.0) <= 1e-15
+    for k in ("root", "gyro", "accel"):
+        e = np.array([kin_ref.norm_err(got[k][b], want[k][b]) for b in np.flatnonzero(keep & (moving | (k != "gyro")))])
+        assert e.max() <= 2.0 ** -23, k
+    gd, wd = got["dofs"].reshape(B, 4, 6), want["dofs"].reshape(B, 4, 6)
+    e = max(kin_ref.norm_err(gd[b][~cl[b]], wd[b][~cl[b]]) for b in np.flatnonzero(keep & ~cl.all(1)))
+    assert e <= 2.0 ** -23
+    assert np.array_equal(got["touch"][keep], want["touch"][keep])
+    assert np.array_equal(got_rec[:, pr.TICK], st["rec"][:, pr.TICK] + 1)
+
+
+def test_make_states_gives_what_it_gave():
+    """The new builders leave make_states alone: its records replay the golden fixture's
+    (tests/test_gpu_plant.py), and A1 drawn by it stands beyond its reach, which is why the mixed
+    fleet draws the base height from each robot's own legs."""
+    st = pr.make_states(512, seed=21, robot="a1")
+    ref = st["rec"].copy()
+    pr.plant_step(ref, st["tau"], st["robot"], st["geom"], pr.Params())
+    assert (ref[:, pr.FLAGS] != 0).any()
+    # weighted sums of what it returned before the new builders came (the cases, the records, the
+    # torques): a draw added, dropped or moved in its sequence changes them in the first digit
+    for (B, kw), (cases, rec, tau) in ((((512, dict(seed=6))), (159479, 4737.5668883353665, 226.85155916317117)),
+                                       ((8, dict(seed=0)), (2452, -896.8553727690638, 77.48438029981122)),
+                                       ((512, dict(seed=21, robot="a1")), (154924, 3117.150495678319, 735.7598306831137))):
+        st = pr.make_states(B, **kw)
+        w = np.cos(np.arange(st["rec"].size)).reshape(st["rec"].shape)
+        assert int(st["case"].astype(np.int64).dot(5 ** np.arange(4)).sum()) == cases
+        assert abs((st["rec"] * w).sum() - rec) <= 1e-9 and abs((st["tau"].astype(np.float64) * w[:, :12]).sum() - tau) <= 1e-9
+        assert (st["robot"] == st["robot"][0]).all() and (st["geom"] == st["geom"][0]).all()
+
+
+@pytest.mark.parametrize("scale", [2.0, 0.5])
+def test_a_record_quaternion_off_unit_length_is_applied_as_given(header, scale):
+    """kin_quat2matrix and kin_ref.quat2matrix_eigen apply the quaternion as given (the ABI asks
+    for no unit length, only a non-zero one): the header and the restatement agree on a record
+    whose quaternion has norm 2 or 0.5, status OK, and the quaternion they leave is of unit
+    length (plant_quat_step normalises)."""
+    par = pr.Params()
+    st = pr.make_states(16, seed=9, par=par)
+    rec = st["rec"].copy()
+    rec[:, pr.QUAT:pr.QUAT + 4] *= scale
+    rec[:, pr.CONTACT:pr.CONTACT + 4] = 0.0               # the feet of the unit pose are far from the scaled one's legs
+    ref, got_rec = rec.copy(), rec.copy()
+    tau = np.zeros_like(st["tau"])                        # and some are at a clamp: no torque through J_b^-1
+    want = pr.plant_step(ref, tau, st["robot"], st["geom"], par)
+    got = run_header(header, got_rec, tau, st["robot"], st["geom"], par)
+    assert (want["status"] == 0).all() and (got["status"] == 0).all()
+    body = slice(0, pr.FEET)
+    assert np.abs(got_rec[:, body] - ref[:, body]).max() <= CPU_BOUND * np.abs(ref[:, body]).max()
+    assert np.array_equal(got_rec[:, pr.CONTACT:pr.WORDS], ref[:, pr.CONTACT:pr.WORDS])
+    assert np.abs(np.linalg.norm(ref[:, pr.QUAT:pr.QUAT + 4], axis=1) - 1.0).max() <= 1e-15
+    for k in ("root", "gyro", "accel"):
+        assert max(kin_ref.norm_err(got[k][b], want[k][b]) for b in range(16)) <= 2.0 ** -23, k
+
+
 def test_reset_matches_the_restatement(header):
     B = 64
     par = pr.Params(contact_tol=2e-3)
