@@ -994,18 +994,29 @@ int mpcqp_set_stance_range(mpcqp_ctx* ctx, int32_t min_stance, int32_t max_stanc
   return MPCQP_OK;
 }
 
+// What every kernel takes from the context: the horizon, dt and the weights.  The kernels that
+// evaluate a given U (mpcqp_predict, mpcqp_certify) take nothing else; enqueue_solve adds what
+// is the solve's.
+static KParams eval_params(const mpcqp_ctx* ctx) {
+  KParams kp;
+  kp.N = ctx->params.horizon;
+  kp.max_iter = 0;
+  kp.dt = ctx->params.dt;
+  for (int i = 0; i < NX; ++i) kp.q[i] = ctx->params.q_diag[i];
+  for (int i = 0; i < NU; ++i) kp.r[i] = ctx->params.r_diag[i];
+  kp.wfull = ctx->wdev;
+  kp.warm = nullptr;
+  kp.warm_cap = 0;
+  return kp;
+}
+
 // Everything mpcqp_solve enqueues on `stream`, for mpcqp_solve and mpcqp_step: the arguments are
 // checked (batch > 0, no NULL required pointer) and the context's device is current.
 static int enqueue_solve(mpcqp_ctx* ctx, int32_t batch, const float* x0, const float* xref, const float* contact,
                          const float* feet, const float* robot, float* u0, float* U, int32_t* status,
                          int32_t* iters, void* stream) {
-  KParams kp;
-  kp.N = ctx->params.horizon;
+  KParams kp = eval_params(ctx);
   kp.max_iter = ctx->params.max_iter;
-  kp.dt = ctx->params.dt;
-  for (int i = 0; i < NX; ++i) kp.q[i] = ctx->params.q_diag[i];
-  for (int i = 0; i < NU; ++i) kp.r[i] = ctx->params.r_diag[i];
-  kp.wfull = ctx->wdev;
   kp.warm = ctx->warm;
   kp.warm_cap = ctx->warm_cap;
   const bool full = ctx->wdev != nullptr;   // the dense classes' full-weight instantiations
@@ -1595,69 +1606,48 @@ int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos
   return launched(ctx, "terrain launch");
 }
 
-// What the kernels that evaluate a given U (mpcqp_predict, mpcqp_certify) take from the context:
-// the horizon, dt and the weights; nothing of the solve.
-static KParams eval_params(const mpcqp_ctx* ctx) {
-  KParams kp;
-  kp.N = ctx->params.horizon;
-  kp.max_iter = 0;
-  kp.dt = ctx->params.dt;
-  for (int i = 0; i < NX; ++i) kp.q[i] = ctx->params.q_diag[i];
-  for (int i = 0; i < NU; ++i) kp.r[i] = ctx->params.r_diag[i];
-  kp.wfull = ctx->wdev;
-  kp.warm = nullptr;
-  kp.warm_cap = 0;
-  return kp;
+// One launch of a kernel that evaluates a given U, one wavefront per robot: mpcqp_predict_kernel
+// or mpcqp_certify_kernel, instantiations `k` in the order <16, false>, <16, true>, <kMaxN, false>,
+// <kMaxN, true>.  `what` names the call in the error texts; `out` is X or G.
+using EvalKernel = void (*)(KParams, int, const float*, const float*, const float*, const float*, const float*,
+                            const float*, float*, double*, int32_t*);
+static int launch_eval(mpcqp_ctx* ctx, const char* what, const EvalKernel (&k)[4], int32_t batch, int32_t flags,
+                       const float* x0, const float* xref, const float* contact, const float* feet,
+                       const float* robot, const float* U, float* out, double* report, int32_t* status,
+                       void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  const std::string w(what);
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown " + w + " flags");
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, w + ": batch < 0");
+  if (!x0 || !xref || !contact || !feet || !robot || !U) return set_err(ctx, MPCQP_ERR_ARG, "null " + w + " input pointer");
+  if (batch == 0 || (!out && !report && !status)) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  const KParams kp = eval_params(ctx);
+  // the instantiation whose LDS holds this horizon and these weights
+  hipLaunchKernelGGL(k[2 * (kp.N > 16) + (kp.wfull != nullptr)], dim3(batch), dim3(LANES), 0, (hipStream_t)stream, kp,
+                     (int)batch, x0, xref, contact, feet, robot, U, out, report, status);
+  return launched(ctx, (w + " launch").c_str());
 }
 
 // The trajectory the QP believes a force sequence produces (com_traj = Sx x0 + Su U,
-// mpc.py:293-294), its cost, cone margin and swing residual: one launch, one wavefront per robot.
+// mpc.py:293-294), its cost, cone margin and swing residual (mpcqp_predict.h).
 int mpcqp_predict(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0, const float* xref,
                   const float* contact, const float* feet, const float* robot, const float* U, float* X,
                   double* report, int32_t* status, void* stream) {
-  if (!ctx) return MPCQP_ERR_ARG;
-  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown predict flags");
-  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "predict: batch < 0");
-  if (!x0 || !xref || !contact || !feet || !robot || !U)
-    return set_err(ctx, MPCQP_ERR_ARG, "null predict input pointer");
-  if (batch == 0 || (!X && !report && !status)) return MPCQP_OK;
-  DeviceScope dev(ctx->device);
-  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
-  const KParams kp = eval_params(ctx);
-  const bool full = kp.wfull != nullptr;
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(batch), dim3(LANES), 0, (hipStream_t)stream, kp, (int)batch, x0, xref, contact, feet,
-                       robot, U, X, report, status);
-  };
-  // the instantiation whose LDS holds this horizon and these weights
-  if (kp.N <= 16) full ? launch(mpcqp_predict_kernel<16, true>) : launch(mpcqp_predict_kernel<16, false>);
-  else full ? launch(mpcqp_predict_kernel<kMaxN, true>) : launch(mpcqp_predict_kernel<kMaxN, false>);
-  return launched(ctx, "predict launch");
+  static const EvalKernel k[4] = {mpcqp_predict_kernel<16, false>, mpcqp_predict_kernel<16, true>,
+                                  mpcqp_predict_kernel<kMaxN, false>, mpcqp_predict_kernel<kMaxN, true>};
+  return launch_eval(ctx, "predict", k, batch, flags, x0, xref, contact, feet, robot, U, X, report, status, stream);
 }
 
 // The gradient of the QP's objective at a force sequence, the objective and the duality gap the
-// friction pyramids give in closed form (mpcqp_certify.h): one launch, one wavefront per robot.
+// friction pyramids give in closed form (mpcqp_certify.h).
 int mpcqp_certify(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* x0, const float* xref,
                   const float* contact, const float* feet, const float* robot, const float* U, float* G,
                   double* report, int32_t* status, void* stream) {
-  if (!ctx) return MPCQP_ERR_ARG;
-  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown certify flags");
-  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "certify: batch < 0");
-  if (!x0 || !xref || !contact || !feet || !robot || !U)
-    return set_err(ctx, MPCQP_ERR_ARG, "null certify input pointer");
-  if (batch == 0 || (!G && !report && !status)) return MPCQP_OK;
-  DeviceScope dev(ctx->device);
-  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
-  const KParams kp = eval_params(ctx);
-  const bool full = kp.wfull != nullptr;
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(batch), dim3(LANES), 0, (hipStream_t)stream, kp, (int)batch, x0, xref, contact, feet,
-                       robot, U, G, report, status);
-  };
-  // the instantiation whose LDS holds this horizon and these weights
-  if (kp.N <= 16) full ? launch(mpcqp_certify_kernel<16, true>) : launch(mpcqp_certify_kernel<16, false>);
-  else full ? launch(mpcqp_certify_kernel<kMaxN, true>) : launch(mpcqp_certify_kernel<kMaxN, false>);
-  return launched(ctx, "certify launch");
+  static const EvalKernel k[4] = {mpcqp_certify_kernel<16, false>, mpcqp_certify_kernel<16, true>,
+                                  mpcqp_certify_kernel<kMaxN, false>, mpcqp_certify_kernel<kMaxN, true>};
+  return launch_eval(ctx, "certify", k, batch, flags, x0, xref, contact, feet, robot, U, G, report, status, stream);
 }
 
 // ---- the rigid-body plant (mpcqp_plant.h): the stage the reference's scripts hand to a simulator

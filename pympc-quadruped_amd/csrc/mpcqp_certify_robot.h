@@ -80,62 +80,19 @@ __host__ __device__ inline double cert_foot_term(const double* fr, double mu, do
 
 #ifndef __HIPCC__
 // One robot on the host: what one wavefront of mpcqp_certify_kernel computes, with the sums over
-// the wave taken in index order.  q, r, W as prd_robot_host.  Gf (float32), Gd (the entries
-// before their rounding), report and status are nullable.
+// the wave taken in index order: prd_rollout_host (J and J_free are prd_robot_host's to the bit),
+// then the backward scan, the gradient and the foot-step terms.  q, r, W as prd_rollout_host.  Gf
+// (float32), Gd (the entries before their rounding), report and status are nullable.
 inline void cert_robot_host(int N, double h, const double* q, const double* r, const double* W, const float* x0,
                             const float* xref, const float* contact, const float* feet, const float* robot,
                             const float* U, float* Gf, double* Gd, double* report, int32_t* status) {
-  bool bad = false;
-  for (int i = 0; i < PRD_NX; ++i) bad |= prd_bad_value(x0[i], false);
-  for (int i = 0; i < 12; ++i) bad |= prd_bad_value(feet[i], false) || prd_bad_value(robot[i], false);
-  for (int i = 0; i < 4 * N; ++i) bad |= prd_bad_value(contact[i], true);
-  for (int i = 0; i < PRD_NX * N; ++i) bad |= prd_bad_value(xref[i], false);
-  for (int i = 0; i < PRD_NU * N; ++i) bad |= prd_bad_value(U[i], false);
-  double c = 0.0, s = 0.0, inv[9], K[3 * PRD_NU], G[3 * PRD_NU], fr[9], n1[PRD_NX], n2[PRD_NX];
-  static thread_local double P[PRD_MAX_N][PRD_NU][2], E[PRD_MAX_N][PRD_NX][2], S[PRD_MAX_N][PRD_NX][2],
-      gd[PRD_MAX_N * PRD_NU];
+  static thread_local PrdRollout ro;
+  static thread_local double S[PRD_MAX_N][PRD_NX][2], gd[PRD_MAX_N * PRD_NU];
   double rep[CERT_REPORT] = {0.0, 0.0, 0.0, 0.0};
-  bool finite = !bad;
-  if (!bad) {
-    prd_yaw(x0, &c, &s);
-    prd_inertia_inv(c, s, robot, inv);
-    const double minv = prd_minv(robot);
-    for (int col = 0; col < PRD_NU; ++col) {
-      double k[3], g[3];
-      prd_kg_column(c, s, inv, feet, col, k, g);
-      for (int a = 0; a < 3; ++a) K[PRD_NU * a + col] = k[a], G[PRD_NU * a + col] = g[a];
-    }
+  bool finite = prd_rollout_host(N, h, q, r, W, x0, xref, contact, feet, robot, U, &ro, S);
+  if (finite) {
+    double fr[9];
     for (int e = 0; e < 9; ++e) fr[e] = cert_frame_entry(robot, e / 3, e % 3);
-    for (int sc = 0; sc < PRD_NX; ++sc) n1[sc] = prd_n1(x0, c, s, h, sc), n2[sc] = prd_n2(x0, h, sc);
-    for (int col = 0; col < PRD_NU; ++col) {
-      double p0 = 0.0, p1 = 0.0;
-      for (int t = 0; t < N; ++t) {
-        prd_scan_step(&p0, &p1, U[PRD_NU * t + col]);
-        P[t][col][0] = p0, P[t][col][1] = p1;
-      }
-    }
-    // e_t, Q e_t (into S[t][.][0]) and the two costs, as prd_robot_host takes them
-    double je = 0.0, jf = 0.0, ju = 0.0;
-    for (int e = 0; e < PRD_NX * N; ++e) {
-      const int t = e / PRD_NX, sc = e % PRD_NX;
-      const double xf = prd_free_entry((double)x0[sc], n1[sc], n2[sc], t);
-      const double x = xf + prd_forced_entry(K, G, minv, h, sc, &P[t][0][0]);
-      E[t][sc][0] = x - (double)xref[e], E[t][sc][1] = xf - (double)xref[e];
-      if (!W) {
-        const double qe = q[sc] * E[t][sc][0];
-        S[t][sc][0] = qe;
-        je += qe * E[t][sc][0], jf += q[sc] * E[t][sc][1] * E[t][sc][1];
-      }
-    }
-    if (W) {
-      for (int e = 0; e < PRD_NX * N; ++e) {
-        const int t = e / PRD_NX, sc = e % PRD_NX;
-        double a = 0.0, af = 0.0;
-        for (int j = 0; j < PRD_NX; ++j) a += W[PRD_NX * sc + j] * E[t][j][0], af += W[PRD_NX * sc + j] * E[t][j][1];
-        S[t][sc][0] = a;
-        je += E[t][sc][0] * a, jf += E[t][sc][1] * af;
-      }
-    }
     // the backward scan: S[j][.][0] holds Q e_j until S0_j replaces it
     for (int sc = 0; sc < PRD_NX; ++sc) {
       double s0 = 0.0, s1 = 0.0;
@@ -145,15 +102,7 @@ inline void cert_robot_host(int N, double h, const double* q, const double* r, c
       }
     }
     for (int e = 0; e < PRD_NU * N; ++e) {
-      const int t = e / PRD_NU, col = e % PRD_NU;
-      double ru = 0.0;
-      if (W) {
-        for (int j = 0; j < PRD_NU; ++j) ru += W[PRD_NX * PRD_NX + PRD_NU * col + j] * (double)U[PRD_NU * t + j];
-      } else {
-        ru = r[col] * (double)U[e];
-      }
-      ju += (double)U[e] * ru;
-      gd[e] = 2.0 * cert_state_grad(K, G, minv, h, col, &S[t][0][0]) + 2.0 * ru;
+      gd[e] = 2.0 * cert_state_grad(ro.K, ro.G, ro.minv, h, e % PRD_NU, &S[e / PRD_NU][0][0]) + 2.0 * ro.ru[e];
       if (!isfinite((float)gd[e])) finite = false;
     }
     double gap = 0.0, worst = -INFINITY;
@@ -165,7 +114,7 @@ inline void cert_robot_host(int N, double h, const double* q, const double* r, c
       gap += term;
       worst = term > worst ? term : worst;
     }
-    rep[CERT_OBJECTIVE] = (je + ju) - jf, rep[CERT_GAP] = gap;
+    rep[CERT_OBJECTIVE] = (ro.je + ro.ju) - ro.jf, rep[CERT_GAP] = gap;
     rep[CERT_LOWER] = rep[CERT_OBJECTIVE] - gap, rep[CERT_WORST] = worst;
     for (int k = 0; k < CERT_REPORT; ++k)
       if (!isfinite(rep[k])) finite = false;

@@ -17,6 +17,9 @@
 //            for the full-Q cost alone
 //   report   per-lane partial sums of the cost, minimum of the slacks, maximum of the swing
 //            entries, reduced across the wave with __shfl_xor; no atomics
+// Stage, head, scan and the error part of the entries are the rollout_* functions below, written
+// once for this kernel and mpcqp_certify_kernel (mpcqp_certify.h), with the store epilogue; what
+// a kernel does with its cone lanes and with each entry it hands them as a lambda.
 // The model is the head of form_model restated (mpcqp_predict_robot.h), not a call of it: a
 // FormT<32> / FormY / RobotMetaT<32> instantiation carries the suffix sums, the Hessian blocks and
 // the full-weight work of the solve, 32 KB of LDS before U and the scans are added where this
@@ -32,24 +35,30 @@ static_assert(PRD_STATUS_OK == MPCQP_STATUS_OK && PRD_STATUS_NONFINITE == MPCQP_
 // entries of X per lane: 4 at NM = 16, 7 at NM = 32
 constexpr int predict_per_lane(int NM) { return (NX * NM + LANES - 1) / LANES; }
 
-// Per-robot LDS, sized for horizons N <= NM (NM = 16 or 32, as the interior-point class sizes its
-// own) and, FULL alone, for the full weights: 6 544 bytes at <16, false>, 20 416 at <32, true>
-// (DESIGN.md 4.4h).  What a launch needs decides how many robots a CU holds at once.
+// Per-robot LDS of the rollout, what mpcqp_predict_kernel and mpcqp_certify_kernel both stage and
+// compute, sized for horizons N <= NM (NM = 16 or 32, as the interior-point class sizes its own)
+// and, FULL alone, for the full weights.  What a launch needs decides how many robots a CU holds
+// at once.
 template <int NM, bool FULL>
-struct alignas(16) PredictShared {
+struct alignas(16) RolloutShared {
   static constexpr int IN_XREF = IN_CONTACT + 4 * NM, IN_END = IN_XREF + NX * NM;
   float in[IN_END];              // staged inputs, form_stage's layout (x0, feet, record, contact, xref)
   float u[NU * NM];              // staged U
   double K[3 * NU];              // inv(I_w)[r_leg]x, float32-rounded
   double G[3 * NU];              // R_z^T K
-  double rows[18];               // one-sided cone rows, [6][3]
   double n1[16], n2[16];         // Nm x0, Nm^2 x0
   double q[16], r[NU];           // diagonal weights
   double minv;                   // float32(1/m)
   double pad;
   double P[NM][NU][2];           // (P0_t, P1_t) per input column
-  double E[FULL ? NM : 1][NX][2];               // (e_t, e_t for U = 0): the full-Q cost reads them back
+  double E[FULL ? NM : 1][NX][2];               // (e_t, e_t for U = 0): the full-Q pass reads them back
   double W[FULL ? NX * NX + NU * NU : 2];       // full Q then R (KParams::wfull)
+};
+
+// The rollout and the cone rows: 6 544 bytes at <16, false>, 20 416 at <32, true>.
+template <int NM, bool FULL>
+struct alignas(16) PredictShared : RolloutShared<NM, FULL> {
+  double rows[18];               // one-sided cone rows, [6][3]
 };
 static_assert(sizeof(PredictShared<kMaxN, true>) == 20416 && sizeof(PredictShared<16, false>) == 6544,
               "DESIGN.md 4.4h states the LDS sizes");
@@ -100,6 +109,142 @@ __device__ __forceinline__ double predict_wave_max(double v) {
   return v;
 }
 
+// ---- the rollout both kernels run, each piece once.  sm: a PredictShared or a CertifyShared.
+
+// stage: the six input slices.  Returns, wave-uniform, whether the robot is taken: a refused
+// robot computes nothing.
+template <class Shared>
+__device__ __forceinline__ bool rollout_stage(Shared& sm, int N, int b, int lane, const float* __restrict__ x0g,
+                                              const float* __restrict__ xrefg, const float* __restrict__ contactg,
+                                              const float* __restrict__ feetg, const float* __restrict__ robotg,
+                                              const float* __restrict__ Ug) {
+  const bool bad_u = predict_stage_u(sm.u, Ug + (size_t)b * N * NU, NU * N, lane);
+  const bool ok_in = form_stage<LANES>(sm, N, b, lane, x0g, xrefg, contactg, feetg, robotg);
+  const bool finite = ok_in && !__any(bad_u);
+  fsync<LANES>();   // the staged slices are read by other lanes below
+  return finite;
+}
+
+// head and forward scan, to the sync after which every lane may read them.  Lanes 0..11 one column
+// of K and G and, after it, that input column's running sums; lanes 12..12 + CONE - 1 are the
+// caller's, cone(lane - 12), for its form of the cone (predict: the 18 row entries, certify: the
+// 9 of the frame); lanes 32..44 n1 / n2 and the diagonal weights; every lane the full weights if
+// set.  N and h are P's, read by the kernel ahead of the stage so that the loads are not waited
+// for here.
+template <bool FULL, int CONE, class Shared, class Cone>
+__device__ __forceinline__ void rollout_head_scan(Shared& sm, const KParams& P, int N, double h, int lane,
+                                                  Cone&& cone) {
+#pragma clang fp contract(off)
+  static_assert(NU + CONE <= 32, "the cone lanes end where the lanes of n1 / n2 begin");
+  const float* const x0 = sm.in + IN_X0;
+  const float* const rec = sm.in + IN_ROBOT;
+  double c, s;
+  prd_yaw(x0, &c, &s);
+  if (lane < NU) {
+    double inv[9], k[3], g[3];
+    prd_inertia_inv(c, s, rec, inv);
+    prd_kg_column(c, s, inv, sm.in + IN_FEET, lane, k, g);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      sm.K[NU * a + lane] = k[a];
+      sm.G[NU * a + lane] = g[a];
+    }
+    sm.r[lane] = P.r[lane];
+  } else if (lane < NU + CONE) {
+    cone(lane - NU);
+  } else if (lane >= 32 && lane < 32 + NX) {
+    const int sc = lane - 32;
+    sm.n1[sc] = prd_n1(x0, c, s, h, sc);
+    sm.n2[sc] = prd_n2(x0, h, sc);
+    sm.q[sc] = P.q[sc];
+    if (sc == 0) sm.minv = prd_minv(rec);
+  }
+  if constexpr (FULL)
+    for (int e = lane; e < NX * NX + NU * NU; e += LANES) sm.W[e] = P.wfull[e];
+  if (lane < NU) {
+    double p0 = 0.0, p1 = 0.0;
+    for (int t = 0; t < N; ++t) {
+      prd_scan_step(&p0, &p1, sm.u[NU * t + lane]);
+      sm.P[t][lane][0] = p0;
+      sm.P[t][lane][1] = p1;
+    }
+  }
+  fsync<LANES>();
+}
+
+// The 13 N error entries dealt over the lanes, entry e = lane + 64 i: x_{t+1}[sc] for U = 0 and for
+// U, e_t and its U = 0 twin, and this lane's part of the two tracking costs added to *je and
+// *jf.  The full weights go through E and a second pass over W.  The caller is handed
+// state(i, x), x before its float32 rounding, and weighted(t, sc, (Q e_t)[sc]).
+template <int NM, bool FULL, class Shared, class State, class Weighted>
+__device__ __forceinline__ void rollout_errors(Shared& sm, int N, double h, int lane, double* je, double* jf,
+                                               State&& state, Weighted&& weighted) {
+#pragma clang fp contract(off)
+  const float* const x0 = sm.in + IN_X0;
+  const double minv = sm.minv;
+#pragma unroll
+  for (int i = 0; i < predict_per_lane(NM); ++i) {
+    const int e = lane + LANES * i;
+    if (e < NX * N) {
+      const int t = e / NX, sc = e % NX;
+      const double xref = (double)sm.in[Shared::IN_XREF + e];
+      const double xf = prd_free_entry((double)x0[sc], sm.n1[sc], sm.n2[sc], t);
+      const double x = xf + prd_forced_entry(sm.K, sm.G, minv, h, sc, &sm.P[t][0][0]);
+      state(i, x);
+      const double ee = x - xref, ef = xf - xref;
+      if constexpr (FULL) {
+        sm.E[t][sc][0] = ee;
+        sm.E[t][sc][1] = ef;
+      } else {
+        const double qs = sm.q[sc];
+        const double qe = qs * ee;
+        weighted(t, sc, qe);
+        *je += qe * ee;
+        *jf += qs * ef * ef;
+      }
+    }
+  }
+  if constexpr (FULL) {
+    fsync<LANES>();
+    for (int e = lane; e < NX * N; e += LANES) {
+      const int t = e / NX, sc = e % NX;
+      double a = 0.0, af = 0.0;
+#pragma unroll
+      for (int j = 0; j < NX; ++j) {
+        const double w = sm.W[NX * sc + j];
+        a += w * sm.E[t][j][0];
+        af += w * sm.E[t][j][1];
+      }
+      weighted(t, sc, a);
+      *je += sm.E[t][sc][0] * a;
+      *jf += sm.E[t][sc][1] * af;
+    }
+  }
+}
+
+// The stores: the PER float32 entries a lane holds of the robot's WIDTH N (entry e = lane + 64 i),
+// the four report words and the status; a refused robot's entries and report are zeros.
+template <int WIDTH, int PER>
+__device__ __forceinline__ void rollout_store(bool finite, int N, int b, int lane, const float (&v)[PER],
+                                              float* __restrict__ outg, double r0, double r1, double r2, double r3,
+                                              double* __restrict__ reportg, int32_t* __restrict__ statusg) {
+  if (outg != nullptr) {
+    float* const ob = outg + (size_t)b * N * WIDTH;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int e = lane + LANES * i;
+      if (e < WIDTH * N) ob[e] = finite ? v[i] : 0.f;
+    }
+  }
+  if (lane < 4 && reportg != nullptr) {
+    const double w = lane == 0 ? r0 : lane == 1 ? r1 : lane == 2 ? r2 : r3;
+    reportg[(size_t)b * 4 + lane] = finite ? w : 0.0;
+  }
+  if (lane == 0 && statusg != nullptr) statusg[b] = finite ? MPCQP_STATUS_OK : MPCQP_STATUS_NONFINITE;
+}
+static_assert(PRD_REPORT == 4 && PRD_COST == 0 && PRD_COST_FREE == 1 && PRD_MARGIN == 2 && PRD_SWING == 3,
+              "rollout_store takes the report words in their order");
+
 template <int NM, bool FULL>
 __global__ __launch_bounds__(LANES) void mpcqp_predict_kernel(
     KParams P, int B, const float* __restrict__ x0g, const float* __restrict__ xrefg,
@@ -107,100 +252,31 @@ __global__ __launch_bounds__(LANES) void mpcqp_predict_kernel(
     const float* __restrict__ Ug, float* __restrict__ Xg, double* __restrict__ reportg, int32_t* __restrict__ statusg) {
 #pragma clang fp contract(off)   // as mpcqp_predict_robot.h: the host build differs in the wave sums' order alone
   constexpr int kPredictPerLane = predict_per_lane(NM);
-  using Shared = PredictShared<NM, FULL>;
-  __shared__ Shared sm;
+  __shared__ PredictShared<NM, FULL> sm;
   const int b = blockIdx.x;
   if (b >= B) return;
   const int lane = threadIdx.x;
   const int N = P.N;
   const double h = P.dt;
-  constexpr bool full = FULL;
-  // ---- stage: the six input slices; a refused robot computes nothing
-  const bool bad_u = predict_stage_u(sm.u, Ug + (size_t)b * N * NU, NU * N, lane);
-  const bool ok_in = form_stage<LANES>(sm, N, b, lane, x0g, xrefg, contactg, feetg, robotg);
-  bool finite = ok_in && !__any(bad_u);   // wave-uniform
-  fsync<LANES>();                         // the staged slices are read by other lanes below
+  bool finite = rollout_stage(sm, N, b, lane, x0g, xrefg, contactg, feetg, robotg, Ug);
   float xv[kPredictPerLane];
 #pragma unroll
   for (int i = 0; i < kPredictPerLane; ++i) xv[i] = 0.f;
   double cost = 0.0, cost_free = 0.0, margin = 0.0, swing = 0.0;
   if (finite) {
-    const float* const x0 = sm.in + IN_X0;
     const float* const rec = sm.in + IN_ROBOT;
-    // ---- head
-    double c, s;
-    prd_yaw(x0, &c, &s);
-    if (lane < NU) {
-      double inv[9], k[3], g[3];
-      prd_inertia_inv(c, s, rec, inv);
-      prd_kg_column(c, s, inv, sm.in + IN_FEET, lane, k, g);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        sm.K[NU * a + lane] = k[a];
-        sm.G[NU * a + lane] = g[a];
-      }
-      sm.r[lane] = P.r[lane];
-    } else if (lane < NU + 18) {
-      const int e = lane - NU;
-      sm.rows[e] = prd_cone_entry(rec, e / 3, e % 3);
-    } else if (lane >= 32 && lane < 32 + NX) {
-      const int sc = lane - 32;
-      sm.n1[sc] = prd_n1(x0, c, s, h, sc);
-      sm.n2[sc] = prd_n2(x0, h, sc);
-      sm.q[sc] = P.q[sc];
-      if (sc == 0) sm.minv = prd_minv(rec);
-    }
-    if constexpr (full)
-      for (int e = lane; e < NX * NX + NU * NU; e += LANES) sm.W[e] = P.wfull[e];
-    // ---- scan: lanes 0..11, one input column each
-    if (lane < NU) {
-      double p0 = 0.0, p1 = 0.0;
-      for (int t = 0; t < N; ++t) {
-        prd_scan_step(&p0, &p1, sm.u[NU * t + lane]);
-        sm.P[t][lane][0] = p0;
-        sm.P[t][lane][1] = p1;
-      }
-    }
-    fsync<LANES>();
-    // ---- entries of X, 13 N dealt over the lanes
-    const double minv = sm.minv;
+    rollout_head_scan<FULL, 18>(sm, P, N, h, lane, [&](int e) { sm.rows[e] = prd_cone_entry(rec, e / 3, e % 3); });
+    // ---- entries of X, each kept in a register until the robot's status is known
     bool lane_ok = true;
     double je = 0.0, jf = 0.0, ju = 0.0;
-#pragma unroll
-    for (int i = 0; i < kPredictPerLane; ++i) {
-      const int e = lane + LANES * i;
-      if (e < NX * N) {
-        const int t = e / NX, sc = e % NX;
-        const double xref = (double)sm.in[Shared::IN_XREF + e];
-        const double xf = prd_free_entry((double)x0[sc], sm.n1[sc], sm.n2[sc], t);
-        const double x = xf + prd_forced_entry(sm.K, sm.G, minv, h, sc, &sm.P[t][0][0]);
-        xv[i] = (float)x;
-        lane_ok = lane_ok && isfinite(xv[i]);
-        const double ee = x - xref, ef = xf - xref;
-        if constexpr (full) {
-          sm.E[t][sc][0] = ee;
-          sm.E[t][sc][1] = ef;
-        } else {
-          const double qs = sm.q[sc];
-          je += qs * ee * ee;
-          jf += qs * ef * ef;
-        }
-      }
-    }
-    if constexpr (full) {
-      fsync<LANES>();
-      for (int e = lane; e < NX * N; e += LANES) {
-        const int t = e / NX, sc = e % NX;
-        double a = 0.0, af = 0.0;
-#pragma unroll
-        for (int j = 0; j < NX; ++j) {
-          const double w = sm.W[NX * sc + j];
-          a += w * sm.E[t][j][0];
-          af += w * sm.E[t][j][1];
-        }
-        je += sm.E[t][sc][0] * a;
-        jf += sm.E[t][sc][1] * af;
-      }
+    rollout_errors<NM, FULL>(
+        sm, N, h, lane, &je, &jf,
+        [&](int i, double x) {
+          xv[i] = (float)x;
+          lane_ok = lane_ok && isfinite(xv[i]);
+        },
+        [](int, int, double) {});
+    if constexpr (FULL) {
       for (int e = lane; e < NU * N; e += LANES) {
         const int t = e / NU, col = e % NU;
         double a = 0.0;
@@ -242,18 +318,6 @@ __global__ __launch_bounds__(LANES) void mpcqp_predict_kernel(
     swing = predict_wave_max(sw);
     finite = !__any(!lane_ok) && isfinite(cost) && isfinite(cost_free);
   }
-  // ---- stores: a refused robot's X and report are zeros
-  if (Xg != nullptr) {
-    float* const Xb = Xg + (size_t)b * N * NX;
-#pragma unroll
-    for (int i = 0; i < kPredictPerLane; ++i) {
-      const int e = lane + LANES * i;
-      if (e < NX * N) Xb[e] = finite ? xv[i] : 0.f;
-    }
-  }
-  if (lane < PRD_REPORT && reportg != nullptr) {
-    const double v = lane == PRD_COST ? cost : lane == PRD_COST_FREE ? cost_free : lane == PRD_MARGIN ? margin : swing;
-    reportg[(size_t)b * PRD_REPORT + lane] = finite ? v : 0.0;
-  }
-  if (lane == 0 && statusg != nullptr) statusg[b] = finite ? MPCQP_STATUS_OK : MPCQP_STATUS_NONFINITE;
+  rollout_store<NX>(finite, N, b, lane, xv, Xg, cost, cost_free, margin, swing, reportg, statusg);
 }
+

@@ -14,7 +14,9 @@
 //   prd_scan_step    one step of the two running sums of one input column
 //   prd_free_entry, prd_forced_entry   one entry of x_{t+1}: the U = 0 part and the part U adds
 //   prd_foot_slack   the smallest slack of a stance foot-step's six one-sided cone rows
-//   prd_robot_host   (host build only) one robot, entry after entry in the order above
+//   prd_rollout_host (host build only) what the predicted trajectory and the certificate share of
+//                    one robot, entry after entry in the order above: model, sums, errors, costs
+//   prd_robot_host   (host build only) that, then the cone margin and the swing residual
 //
 // Everything is float64 on the caller's float32 inputs; FP contraction is off so the host build
 // and the device build round alike (they differ in the order of the sums over the wave alone).
@@ -201,69 +203,101 @@ __host__ __device__ inline double prd_foot_slack(const double* rows, double ub, 
 __host__ __device__ inline bool prd_bad_value(float w, bool is_contact) { return is_contact ? w == INFINITY : !isfinite(w); }
 
 #ifndef __HIPCC__
-// One robot on the host, entry after entry: what one wavefront of mpcqp_predict_kernel computes,
-// with the sums over the wave taken in index order.  q [13], r [12] the diagonal weights; W the
-// full Q (13 x 13) then R (12 x 12), or NULL.  X, Xd (the entries before their float32 rounding),
-// report and status are nullable.
-inline void prd_robot_host(int N, double h, const double* q, const double* r, const double* W, const float* x0,
-                           const float* xref, const float* contact, const float* feet, const float* robot,
-                           const float* U, float* X, double* Xd, double* report, int32_t* status) {
+// The rollout of one robot on the host, what prd_robot_host and cert_robot_host share: the model
+// head, the forward sums, the entries of X before their rounding, the errors and the three costs,
+// entry after entry in the order a wavefront's lanes take them, the sums over the wave in index
+// order.
+struct PrdRollout {
+  double K[3 * PRD_NU], G[3 * PRD_NU], minv;
+  double P[PRD_MAX_N][PRD_NU][2];   // (P0_t, P1_t) per input column
+  double E[PRD_MAX_N][PRD_NX][2];   // (e_t, e_t for U = 0)
+  double x[PRD_MAX_N * PRD_NX];     // x_{t+1}
+  double ru[PRD_MAX_N * PRD_NU];    // R u
+  double je, jf, ju;                // J = je + ju, J_free = jf
+};
+
+// q [13], r [12] the diagonal weights; W the full Q (13 x 13) then R (12 x 12), or NULL.  S, where
+// the caller asks for it, receives Q e_t in S[t][.][0].  Returns false, with *ro untouched, for
+// the inputs the kernels refuse.
+inline bool prd_rollout_host(int N, double h, const double* q, const double* r, const double* W, const float* x0,
+                             const float* xref, const float* contact, const float* feet, const float* robot,
+                             const float* U, PrdRollout* ro, double (*S)[PRD_NX][2]) {
   bool bad = false;
   for (int i = 0; i < PRD_NX; ++i) bad |= prd_bad_value(x0[i], false);
   for (int i = 0; i < 12; ++i) bad |= prd_bad_value(feet[i], false) || prd_bad_value(robot[i], false);
   for (int i = 0; i < 4 * N; ++i) bad |= prd_bad_value(contact[i], true);
   for (int i = 0; i < PRD_NX * N; ++i) bad |= prd_bad_value(xref[i], false);
   for (int i = 0; i < PRD_NU * N; ++i) bad |= prd_bad_value(U[i], false);
-  double c = 0.0, s = 0.0, inv[9], K[3 * PRD_NU], G[3 * PRD_NU], rows[18], n1[PRD_NX], n2[PRD_NX];
-  static thread_local double P[PRD_MAX_N][PRD_NU][2], E[PRD_MAX_N][PRD_NX][2], xd[PRD_MAX_N * PRD_NX];
-  double rep[PRD_REPORT] = {0.0, 0.0, 0.0, 0.0};
-  bool finite = !bad;
-  if (!bad) {
-    prd_yaw(x0, &c, &s);
-    prd_inertia_inv(c, s, robot, inv);
-    const double minv = prd_minv(robot);
-    for (int col = 0; col < PRD_NU; ++col) {
-      double k[3], g[3];
-      prd_kg_column(c, s, inv, feet, col, k, g);
-      for (int a = 0; a < 3; ++a) K[PRD_NU * a + col] = k[a], G[PRD_NU * a + col] = g[a];
+  if (bad) return false;
+  double c = 0.0, s = 0.0, inv[9], n1[PRD_NX], n2[PRD_NX];
+  prd_yaw(x0, &c, &s);
+  prd_inertia_inv(c, s, robot, inv);
+  ro->minv = prd_minv(robot);
+  for (int col = 0; col < PRD_NU; ++col) {
+    double k[3], g[3];
+    prd_kg_column(c, s, inv, feet, col, k, g);
+    for (int a = 0; a < 3; ++a) ro->K[PRD_NU * a + col] = k[a], ro->G[PRD_NU * a + col] = g[a];
+  }
+  for (int sc = 0; sc < PRD_NX; ++sc) n1[sc] = prd_n1(x0, c, s, h, sc), n2[sc] = prd_n2(x0, h, sc);
+  for (int col = 0; col < PRD_NU; ++col) {
+    double p0 = 0.0, p1 = 0.0;
+    for (int t = 0; t < N; ++t) {
+      prd_scan_step(&p0, &p1, U[PRD_NU * t + col]);
+      ro->P[t][col][0] = p0, ro->P[t][col][1] = p1;
     }
-    for (int e = 0; e < 18; ++e) rows[e] = prd_cone_entry(robot, e / 3, e % 3);
-    for (int sc = 0; sc < PRD_NX; ++sc) n1[sc] = prd_n1(x0, c, s, h, sc), n2[sc] = prd_n2(x0, h, sc);
-    for (int col = 0; col < PRD_NU; ++col) {
-      double p0 = 0.0, p1 = 0.0;
-      for (int t = 0; t < N; ++t) {
-        prd_scan_step(&p0, &p1, U[PRD_NU * t + col]);
-        P[t][col][0] = p0, P[t][col][1] = p1;
-      }
+  }
+  double je = 0.0, jf = 0.0, ju = 0.0;
+  for (int e = 0; e < PRD_NX * N; ++e) {
+    const int t = e / PRD_NX, sc = e % PRD_NX;
+    const double xf = prd_free_entry((double)x0[sc], n1[sc], n2[sc], t);
+    const double x = xf + prd_forced_entry(ro->K, ro->G, ro->minv, h, sc, &ro->P[t][0][0]);
+    ro->x[e] = x;
+    const double ee = x - (double)xref[e], ef = xf - (double)xref[e];
+    ro->E[t][sc][0] = ee, ro->E[t][sc][1] = ef;
+    if (!W) {
+      const double qe = q[sc] * ee;
+      if (S) S[t][sc][0] = qe;
+      je += qe * ee, jf += q[sc] * ef * ef;
     }
-    double je = 0.0, jf = 0.0, ju = 0.0;
+  }
+  if (W) {
     for (int e = 0; e < PRD_NX * N; ++e) {
       const int t = e / PRD_NX, sc = e % PRD_NX;
-      const double xf = prd_free_entry((double)x0[sc], n1[sc], n2[sc], t);
-      const double x = xf + prd_forced_entry(K, G, minv, h, sc, &P[t][0][0]);
-      xd[e] = x;
-      if (!isfinite((float)x)) finite = false;
-      E[t][sc][0] = x - (double)xref[e], E[t][sc][1] = xf - (double)xref[e];
-      if (!W) je += q[sc] * E[t][sc][0] * E[t][sc][0], jf += q[sc] * E[t][sc][1] * E[t][sc][1];
+      double a = 0.0, af = 0.0;
+      for (int j = 0; j < PRD_NX; ++j) a += W[PRD_NX * sc + j] * ro->E[t][j][0], af += W[PRD_NX * sc + j] * ro->E[t][j][1];
+      if (S) S[t][sc][0] = a;
+      je += ro->E[t][sc][0] * a, jf += ro->E[t][sc][1] * af;
     }
+  }
+  for (int e = 0; e < PRD_NU * N; ++e) {
+    const int t = e / PRD_NU, col = e % PRD_NU;
+    double ru = 0.0;
     if (W) {
-      for (int e = 0; e < PRD_NX * N; ++e) {
-        const int t = e / PRD_NX, sc = e % PRD_NX;
-        double a = 0.0, af = 0.0;
-        for (int j = 0; j < PRD_NX; ++j) a += W[PRD_NX * sc + j] * E[t][j][0], af += W[PRD_NX * sc + j] * E[t][j][1];
-        je += E[t][sc][0] * a, jf += E[t][sc][1] * af;
-      }
+      for (int j = 0; j < PRD_NU; ++j) ru += W[PRD_NX * PRD_NX + PRD_NU * col + j] * (double)U[PRD_NU * t + j];
+    } else {
+      ru = r[col] * (double)U[e];
     }
-    for (int e = 0; e < PRD_NU * N; ++e) {
-      const int t = e / PRD_NU, col = e % PRD_NU;
-      if (W) {
-        double a = 0.0;
-        for (int j = 0; j < PRD_NU; ++j) a += W[PRD_NX * PRD_NX + PRD_NU * col + j] * (double)U[PRD_NU * t + j];
-        ju += (double)U[e] * a;
-      } else {
-        ju += r[col] * (double)U[e] * (double)U[e];
-      }
-    }
+    ro->ru[e] = ru;
+    ju += (double)U[e] * ru;
+  }
+  ro->je = je, ro->jf = jf, ro->ju = ju;
+  return true;
+}
+
+// One robot on the host, entry after entry: what one wavefront of mpcqp_predict_kernel computes,
+// with the sums over the wave taken in index order.  q, r, W as prd_rollout_host.  X, Xd (the
+// entries before their float32 rounding), report and status are nullable.
+inline void prd_robot_host(int N, double h, const double* q, const double* r, const double* W, const float* x0,
+                           const float* xref, const float* contact, const float* feet, const float* robot,
+                           const float* U, float* X, double* Xd, double* report, int32_t* status) {
+  static thread_local PrdRollout ro;
+  double rep[PRD_REPORT] = {0.0, 0.0, 0.0, 0.0};
+  bool finite = prd_rollout_host(N, h, q, r, W, x0, xref, contact, feet, robot, U, &ro, nullptr);
+  if (finite) {
+    for (int e = 0; e < PRD_NX * N; ++e)
+      if (!isfinite((float)ro.x[e])) finite = false;
+    double rows[18];
+    for (int e = 0; e < 18; ++e) rows[e] = prd_cone_entry(robot, e / 3, e % 3);
     double margin = INFINITY, swing = 0.0;
     for (int k = 0; k < 4 * N; ++k) {
       const float* f = U + 3 * k;
@@ -274,12 +308,12 @@ inline void prd_robot_host(int N, double h, const double* q, const double* r, co
         for (int a = 0; a < 3; ++a) swing = fabs((double)f[a]) > swing ? fabs((double)f[a]) : swing;
       }
     }
-    rep[PRD_COST] = je + ju, rep[PRD_COST_FREE] = jf, rep[PRD_MARGIN] = margin, rep[PRD_SWING] = swing;
+    rep[PRD_COST] = ro.je + ro.ju, rep[PRD_COST_FREE] = ro.jf, rep[PRD_MARGIN] = margin, rep[PRD_SWING] = swing;
     if (!isfinite(rep[PRD_COST]) || !isfinite(rep[PRD_COST_FREE])) finite = false;
   }
   for (int e = 0; e < PRD_NX * N; ++e) {
-    if (X) X[e] = finite ? (float)xd[e] : 0.f;
-    if (Xd) Xd[e] = finite ? xd[e] : 0.0;
+    if (X) X[e] = finite ? (float)ro.x[e] : 0.f;
+    if (Xd) Xd[e] = finite ? ro.x[e] : 0.0;
   }
   for (int k = 0; k < PRD_REPORT; ++k)
     if (report) report[k] = finite ? rep[k] : 0.0;

@@ -1,5 +1,5 @@
-"""Shared test helpers: oracle solutions for synthetic batches (CPU, float64), and the
-symbols include/mpcqp.h declares."""
+"""Shared test helpers: oracle solutions for synthetic batches (CPU, float64), the symbols
+include/mpcqp.h declares, and the prototypes of a header."""
 import os
 import re
 
@@ -15,6 +15,29 @@ def _declared():
     """The name of every function include/mpcqp.h declares."""
     src = open(HEADER).read()
     return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
+
+
+def _prototypes(header):
+    """{name: (return type, [parameter types])} of the header at that path, comments removed; a
+    type is the declaration's text less the parameter's name, "T*" for every pointer."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(header).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(mpcqp_\w+)\s*\(([^)]*)\)\s*;", src, re.M):
+        kinds = []
+        for prm in params.split(","):
+            prm = " ".join(prm.split())
+            if prm == "void" and "," not in params:
+                continue
+            kinds.append("T*" if "*" in prm else re.sub(r"\s*\w+$", "", prm))
+        out[name] = ("T*" if "*" in ret else ret.strip(), kinds)
+    return out
+
+
+def _int_prototypes(header):
+    """{name: [parameter types]} of a companion header, every function of which returns int."""
+    protos = _prototypes(header)
+    assert all(ret == "int" for ret, _ in protos.values()), protos
+    return {name: kinds for name, (_, kinds) in protos.items()}
 
 
 def oracle_solution(batch, b, horizon, Q=F.Q_DIAG, R=F.R_DIAG):

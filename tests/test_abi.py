@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from helpers import _declared
+from helpers import _declared, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
@@ -15,22 +15,6 @@ HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 def test_header_and_binding_agree():
     from mpcqp import _lib
     assert sorted(_declared()) == sorted(_lib.EXPORTED_SYMBOLS)
-
-
-def _prototypes():
-    """{name: (return type, [parameter types])} of include/mpcqp.h, comments removed; a type is
-    the declaration's text less the parameter's name, "T*" for every pointer."""
-    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(mpcqp_\w+)\s*\(([^)]*)\)\s*;", src, re.M):
-        kinds = []
-        for prm in params.split(","):
-            prm = " ".join(prm.split())
-            if prm == "void" and "," not in params:
-                continue
-            kinds.append("T*" if "*" in prm else re.sub(r"\s*\w+$", "", prm))
-        out[name] = ("T*" if "*" in ret else ret.strip(), kinds)
-    return out
 
 
 def _is_pointer(t):
@@ -46,7 +30,7 @@ def test_binding_signatures_match_the_header():
     position: a pointer is passed as a pointer, int32_t as a 32-bit int, double as c_double, and
     the return type likewise.  A miscounted row would hand a kernel garbage pointers."""
     from mpcqp import _lib
-    protos = _prototypes()
+    protos = _prototypes(HEADER)
     assert set(protos) == _declared() == set(_lib.SIGNATURES) and len(protos) == 28
     agrees = {"T*": _is_pointer, "int32_t": _is_int32, "int": _is_int32, "double": lambda t: t is ctypes.c_double}
     for name, (ret, kinds) in protos.items():

@@ -32,7 +32,7 @@ import pytest
 
 import certify_ref as cr
 import predict_ref as pr
-from helpers import _declared, oracle_solution
+from helpers import _declared, _int_prototypes, oracle_solution
 from oracle import formulation as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,6 +54,14 @@ extern "C" void launch(int N, double h, const double* q, const double* r, const 
                     U + 12 * N * b, G ? G + 12 * N * b : nullptr, Gd ? Gd + 12 * N * b : nullptr,
                     report ? report + CERT_REPORT * b : nullptr, status ? status + b : nullptr);
 }
+// the predicted trajectory's report and status on the same inputs (mpcqp_predict_robot.h)
+extern "C" void launch_predict(int N, double h, const double* q, const double* r, const double* W, int B,
+                               const float* x0, const float* xref, const float* contact, const float* feet,
+                               const float* robot, const float* U, double* report, int32_t* status) {
+  for (int b = 0; b < B; ++b)
+    prd_robot_host(N, h, q, r, W, x0 + 13 * b, xref + 13 * N * b, contact + 4 * N * b, feet + 12 * b, robot + 16 * b,
+                   U + 12 * N * b, nullptr, nullptr, report + PRD_REPORT * b, status + b);
+}
 extern "C" int report_words(void) { return CERT_REPORT; }
 extern "C" int report_word(int k) { return k == 0 ? CERT_OBJECTIVE : k == 1 ? CERT_GAP : k == 2 ? CERT_LOWER : CERT_WORST; }
 extern "C" int status_nonfinite(void) { return PRD_STATUS_NONFINITE; }
@@ -63,23 +71,12 @@ extern "C" int max_horizon(void) { return PRD_MAX_N; }
 
 # ---- the ABI and Python surface
 
-def _certify_prototypes():
-    """{name: [parameter kinds]} of include/mpcqp_certify_abi.h, comments removed: "T*" for a
-    pointer, else the declared type (as tests/test_abi.py reads include/mpcqp.h)."""
-    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(CERTIFY_HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(mpcqp_\w+)\s*\(([^)]*)\)\s*;", src, re.M):
-        assert ret.strip() == "int", (name, ret)
-        out[name] = ["T*" if "*" in p else re.sub(r"\s*\w+$", "", " ".join(p.split())) for p in params.split(",")]
-    return out
-
-
 def test_header_declares_certify_and_binding_agrees():
     """mpcqp_certify is declared in the companion header include/mpcqp_certify_abi.h alone (mpcqp.h
     and its binding table keep their functions, which tests/test_abi.py pins), and its binding
     row agrees with the declaration position by position."""
     from mpcqp import _lib
-    protos = _certify_prototypes()
+    protos = _int_prototypes(CERTIFY_HEADER)
     assert set(protos) == {"mpcqp_certify"} == set(_lib.CERTIFY_SIGNATURES)
     assert _declared() == set(_lib.EXPORTED_SYMBOLS) and "mpcqp_certify" not in _declared()
     restype, argtypes = _lib.CERTIFY_SIGNATURES["mpcqp_certify"]
@@ -243,6 +240,8 @@ def robot(tmp_path_factory):
     vp = ctypes.c_void_p
     lib.launch.argtypes = [ctypes.c_int, ctypes.c_double, vp, vp, vp, ctypes.c_int] + [vp] * 10
     lib.launch.restype = None
+    lib.launch_predict.argtypes = [ctypes.c_int, ctypes.c_double, vp, vp, vp, ctypes.c_int] + [vp] * 8
+    lib.launch_predict.restype = None
     return lib
 
 
@@ -250,10 +249,8 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def host_launch(lib, N, bt, U, Q=cr.Q_DIAG, R=cr.R_DIAG, dt=cr.DT, pad=2, skip=()):
-    """A launch on the host: the outputs come back with `pad` sentinel rows; `skip`: outputs passed
-    as NULL."""
-    B = len(bt["x0"])
+def _weights(Q, R):
+    """(q, r, W) as the host bodies take them: the diagonals, and the full Q then R or None."""
     Q, R = np.asarray(Q, np.float64), np.asarray(R, np.float64)
     W = None
     if Q.ndim == 2 or R.ndim == 2:
@@ -261,11 +258,19 @@ def host_launch(lib, N, bt, U, Q=cr.Q_DIAG, R=cr.R_DIAG, dt=cr.DT, pad=2, skip=(
         Rm = R if R.ndim == 2 else np.diag(R)
         W = np.ascontiguousarray(np.concatenate([Qm.reshape(-1), Rm.reshape(-1)]))
         Q, R = np.diag(Qm).copy(), np.diag(Rm).copy()
+    return np.ascontiguousarray(Q), np.ascontiguousarray(R), W
+
+
+def host_launch(lib, N, bt, U, Q=cr.Q_DIAG, R=cr.R_DIAG, dt=cr.DT, pad=2, skip=()):
+    """A launch on the host: the outputs come back with `pad` sentinel rows; `skip`: outputs passed
+    as NULL."""
+    B = len(bt["x0"])
+    Q, R, W = _weights(Q, R)
     c = lambda k: np.ascontiguousarray(bt[k], np.float32)
     out = dict(G=np.full((B + pad, N, 12), SENTINEL, np.float32), G64=np.full((B + pad, N, 12), float(SENTINEL)),
                report=np.full((B + pad, 4), float(SENTINEL)), status=np.full((B + pad,), SENTINEL, np.int32))
     a = {k: (None if k in skip else v) for k, v in out.items()}
-    lib.launch(N, dt, _p(np.ascontiguousarray(Q)), _p(np.ascontiguousarray(R)), _p(W), B, _p(c("x0")), _p(c("xref")),
+    lib.launch(N, dt, _p(Q), _p(R), _p(W), B, _p(c("x0")), _p(c("xref")),
                _p(c("contact")), _p(c("feet")), _p(c("robot")), _p(np.ascontiguousarray(U, np.float32)), _p(a["G"]),
                _p(a["G64"]), _p(a["report"]), _p(a["status"]))
     for k, v in out.items():
@@ -296,6 +301,27 @@ def test_header_matches_the_restatement(robot):
           f"D_GAP = {dp:.2e} (certify_ref.D_GAP = {cr.D_GAP:.1e})")
     assert dg <= 64 * 2.0 ** -52 and do <= 64 * 2.0 ** -52
     assert dg <= 4 * cr.D_G and do <= 4 * cr.D_OBJ and dp <= 4 * cr.D_GAP      # the recorded figures still describe it
+
+
+def test_objective_is_predicts_cost_difference_to_the_bit(robot):
+    """cert_robot_host's objective is prd_robot_host's cost - cost_free bitwise, and the statuses
+    agree: both take J and J_free from prd_rollout_host, as both kernels take them from the same
+    rollout_* functions (tests/test_gpu_certify.py asserts the same of the device)."""
+    for name in ("short_N1", "mixed_N10", "long_N32", "full_N10", "full_N32"):
+        case = cr.gpu_cases()[name]
+        N, bt, U = case["N"], case["bt"], case["U"]
+        B = len(U)
+        out = host_launch(robot, N, bt, U, case["Q"], case["R"])
+        Q, R, W = _weights(case["Q"], case["R"])
+        c = lambda k: np.ascontiguousarray(bt[k], np.float32)
+        report, status = np.full((B, 4), float(SENTINEL)), np.full((B,), SENTINEL, np.int32)
+        robot.launch_predict(N, cr.DT, _p(Q), _p(R), _p(W), B, _p(c("x0")), _p(c("xref")), _p(c("contact")),
+                             _p(c("feet")), _p(c("robot")), _p(np.ascontiguousarray(U, np.float32)), _p(report),
+                             _p(status))
+        assert np.array_equal(status, out["status"]) and (status == 0).all(), name
+        want = report[:, pr.COST] - report[:, pr.COST_FREE]
+        assert want.tobytes() == out["report"][:, cr.OBJECTIVE].tobytes(), name
+        assert np.abs(want).min() > 0, name           # nothing compared is the zero of a refusal
 
 
 def test_optimum_case_is_near_the_optimum():

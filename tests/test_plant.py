@@ -105,24 +105,13 @@ def run_header(lib, rec, tau, robot, geom, par, plane=None):
 
 # ---- the ABI and Python surface
 
-def _prototypes():
-    """{name: [parameter kinds]} of include/mpcqp_plant_abi.h, comments removed: "T*" for a
-    pointer, else the declared type (as tests/test_predict.py reads its header)."""
-    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(PLANT_HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(mpcqp_\w+)\s*\(([^)]*)\)\s*;", src, re.M):
-        assert ret.strip() == "int", (name, ret)
-        out[name] = ["T*" if "*" in p else re.sub(r"\s*\w+$", "", " ".join(p.split())) for p in params.split(",")]
-    return out
-
-
 def test_header_declares_the_plant_and_binding_agrees():
     """mpcqp_plant, mpcqp_plant_reset and mpcqp_set_plant are declared in the companion header
     (mpcqp.h and its binding table keep their functions, which tests/test_abi.py pins), and each
     binding row agrees with its declaration position by position."""
-    from helpers import _declared
+    from helpers import _declared, _int_prototypes
     from mpcqp import _lib
-    protos = _prototypes()
+    protos = _int_prototypes(PLANT_HEADER)
     assert set(protos) == {"mpcqp_plant", "mpcqp_plant_reset", "mpcqp_set_plant"} == set(_lib.PLANT_SIGNATURES)
     assert _declared() == set(_lib.EXPORTED_SYMBOLS) and not set(protos) & _declared()
     ctype = {"T*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "double": ctypes.c_double}

@@ -28,7 +28,7 @@ import numpy as np
 import pytest
 
 import predict_ref as pr
-from helpers import _declared, oracle_solution
+from helpers import _declared, _int_prototypes, oracle_solution
 from oracle import formulation as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,23 +58,12 @@ extern "C" int max_horizon(void) { return PRD_MAX_N; }
 
 # ---- the ABI and Python surface
 
-def _predict_prototypes():
-    """{name: [parameter kinds]} of include/mpcqp_predict_abi.h, comments removed: "T*" for a
-    pointer, else the declared type (as tests/test_abi.py reads include/mpcqp.h)."""
-    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(PREDICT_HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(mpcqp_\w+)\s*\(([^)]*)\)\s*;", src, re.M):
-        assert ret.strip() == "int", (name, ret)
-        out[name] = ["T*" if "*" in p else re.sub(r"\s*\w+$", "", " ".join(p.split())) for p in params.split(",")]
-    return out
-
-
 def test_header_declares_predict_and_binding_agrees():
     """mpcqp_predict is declared in the companion header include/mpcqp_predict_abi.h (mpcqp.h and
     its binding table keep their 28 functions, which tests/test_abi.py pins), and its binding row
     agrees with the declaration position by position."""
     from mpcqp import _lib
-    protos = _predict_prototypes()
+    protos = _int_prototypes(PREDICT_HEADER)
     assert set(protos) == {"mpcqp_predict"} == set(_lib.PREDICT_SIGNATURES)
     assert _declared() == set(_lib.EXPORTED_SYMBOLS) and "mpcqp_predict" not in _declared()
     restype, argtypes = _lib.PREDICT_SIGNATURES["mpcqp_predict"]
