@@ -28,7 +28,7 @@
 // need, so that a CU holds 16 robots and more at N <= 16 with diagonal weights.
 #include "mpcqp_predict_robot.h"
 
-static_assert(PRD_NX == NX && PRD_NU == NU && PRD_MAX_N == kMaxN, "dimensions: mpcqp.hip and mpcqp_predict_robot.h agree");
+static_assert(PRD_NX == NX && PRD_NU == NU && PRD_MAX_N == kMaxN, "dimensions: mpcqp_device.h and mpcqp_predict_robot.h agree");
 static_assert(PRD_REPORT == MPCQP_PREDICT_REPORT, "report stride");
 static_assert(PRD_STATUS_OK == MPCQP_STATUS_OK && PRD_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
 

@@ -1,4 +1,4 @@
-"""Diagnostic (round 5): the dispatch-order key of mpcqp_order_kernel (csrc/mpcqp.hip).
+"""Diagnostic (round 5): the dispatch-order key of mpcqp_order_kernel (csrc/mpcqp_classes.h).
 
 A robot's solve time follows its active-set iteration count.  This script measures, on the
 bench's seeded batches, how well the key |v0 - vref_0| (horizontal velocity error, the

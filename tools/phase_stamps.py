@@ -20,7 +20,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pympc-quadruped_amd"))
 STAMPS_LIB = os.path.join(ROOT, "pympc-quadruped_amd", "mpcqp", "libmpcqp_stamps.so")
-SLOTS = 256          # kStampU64 (mpcqp.hip)
+SLOTS = 256          # kStampU64 (mpcqp_device.h)
 PHASES = ["inputs, model, Ya/Yb, g", "H tile", "sweep H^-1", "active set", "KKT check", "-"]
 # the first phase between its sub-stamps (slots 9..11; wave 0's clock)
 SUBPHASES = ["stage inputs", "stance list", "model (to Ya/Yb)", "g, barrier"]

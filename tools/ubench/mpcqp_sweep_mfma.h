@@ -1,5 +1,5 @@
-// mpcqp_sweep_mfma.h -- class 64's H^-1 sweep on the f64 matrix cores (included by
-// mpcqp.hip inside its anonymous namespace, before mpcqp_solve.h).
+// mpcqp_sweep_mfma.h -- class 64's H^-1 sweep on the f64 matrix cores (included after
+// csrc/mpcqp_device.h and mpcqp_form.h, whose helpers, d4 and fsync it uses: sweep_check.hip).
 //
 // The symmetric sweep of mpcqp_solve.h, blocked by 4 pivots K = {4k .. 4k+3}.  Each
 // single-pivot sweep there is one rank-1 update beta zeta^T of the whole matrix plus
@@ -25,7 +25,7 @@
 // (free during the sweep: H itself stays in the caller's registers and is stored as
 // the drop path's copy afterwards).
 
-// d4: the ext_vector_type(4) double typedef of mpcqp.hip
+// d4: the ext_vector_type(4) double typedef of mpcqp_device.h
 
 // On entry W holds H in the 4 x 8 tile layout (lane (tr, tc) = (tid / 8, tid % 8):
 // rows 4 tr .. 4 tr + 3, columns 8 tc .. 8 tc + 7).  On exit Wout holds the sweep

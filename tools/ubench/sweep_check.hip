@@ -2,8 +2,20 @@
 // single-pivot sweep on random SPD matrices of several sizes and conditionings, and
 // (when tools/ubench/realH.bin / realR.bin exist: 16 padded 64 x 64 stance-reduced
 // Hessians and numpy's -H^-1, float64) on real config-2 Hessians.
-#include "../../pympc-quadruped_amd/csrc/mpcqp.hip"
+// (build from the repository root: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude)
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <type_traits>
+#include <utility>
+
+#include "mpcqp.h"
+#include "../../pympc-quadruped_amd/csrc/mpcqp_solve_plan.h"
+namespace {
+#include "../../pympc-quadruped_amd/csrc/mpcqp_device.h"
+#include "../../pympc-quadruped_amd/csrc/mpcqp_form.h"
 #include "mpcqp_sweep_mfma.h"
+}  // namespace
 
 #include <stdio.h>
 #include <stdlib.h>
