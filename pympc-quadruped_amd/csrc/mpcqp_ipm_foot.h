@@ -8,20 +8,27 @@
 #define __device__
 #endif
 
-// 3x3 inverse by the adjugate (symmetric positive definite arguments)
+// 3x3 inverse of a symmetric positive definite matrix (its lower triangle is read) by
+// A = L D L^T, A^-1 = L^-T D^-1 L^-1: backward stable without pivoting, and positive definite
+// whenever the three pivots are.  (The adjugate loses the determinant to cancellation once one
+// eigenvalue dominates: an interior-point weight Rh + d a a^T with one nearly active row,
+// d = lambda / s >= 1e6 against Rh = 2e-5, came out indefinite on a tilted cone, whose rows
+// are not exact in binary, and the Newton direction with it.)
 __host__ __device__ inline void inv3(const double (&a)[9], double (&o)[9]) {
-  const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
-  const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
-  const double id = 1.0 / det;
-  o[0] = c00 * id;
-  o[3] = c01 * id;
-  o[6] = c02 * id;
-  o[1] = (a[2] * a[7] - a[1] * a[8]) * id;
-  o[4] = (a[0] * a[8] - a[2] * a[6]) * id;
-  o[7] = (a[1] * a[6] - a[0] * a[7]) * id;
-  o[2] = (a[1] * a[5] - a[2] * a[4]) * id;
-  o[5] = (a[2] * a[3] - a[0] * a[5]) * id;
-  o[8] = (a[0] * a[4] - a[1] * a[3]) * id;
+  const double i0 = 1.0 / a[0];
+  const double l10 = a[3] * i0, l20 = a[6] * i0;
+  const double i1 = 1.0 / (a[4] - l10 * a[3]);
+  const double t = a[7] - l20 * a[3];
+  const double l21 = t * i1;
+  const double i2 = 1.0 / (a[8] - l20 * a[6] - l21 * t);
+  const double m20 = l10 * l21 - l20;   // L^-1 = [1 0 0; -l10 1 0; m20 -l21 1]
+  const double w2 = m20 * i2, w1 = l21 * i2;
+  o[8] = i2;
+  o[5] = o[7] = -w1;
+  o[2] = o[6] = w2;
+  o[4] = i1 + l21 * w1;
+  o[1] = o[3] = -l10 * i1 - l21 * w2;
+  o[0] = i0 + l10 * l10 * i1 + m20 * w2;
 }
 
 // Multipliers of one foot-step: the largest min_r lambda_r over the linearly

@@ -1,5 +1,6 @@
 """Shared test helpers: oracle solutions for synthetic batches (CPU, float64), the symbols
-include/mpcqp.h declares, and the prototypes of a header."""
+include/mpcqp.h declares, the prototypes of a header, and the full (non-diagonal) weights the
+parity and the interior-point edge tests share."""
 import os
 import re
 
@@ -60,3 +61,44 @@ def oracle_solution(batch, b, horizon, Q=F.Q_DIAG, R=F.R_DIAG):
 def rel_err_u0(u0, u0_ref):
     """Norm-wise relative error ||u0 - u0*||_inf / max(||u0*||_inf, 1e-3)."""
     return float(np.abs(np.asarray(u0, np.float64) - u0_ref).max() / max(np.abs(u0_ref).max(), 1e-3))
+
+
+def _full_weights(seed, cross_leg_r=False):
+    """A symmetric positive-semidefinite Q coupling the state components (the reference's
+    diagonal scaled by a correlation matrix, |rho| <= 0.4: the weighting keeps the
+    reference's scale, so the float32 condensing of mpc.py:213-230 perturbs the optimum
+    as little as with the diagonal) and a leg-block R (or one with cross-leg terms)."""
+    from mpcqp.params import Q_DIAG, R_DIAG
+    rng = np.random.default_rng(seed)
+    C = np.eye(13)
+    for _ in range(12):
+        i, j = rng.choice(12, size=2, replace=False)   # state 12 (gravity) keeps weight 0
+        C[i, j] = C[j, i] = rng.uniform(-0.4, 0.4)
+    w, V = np.linalg.eigh(C)
+    C = V @ np.diag(np.maximum(w, 0.05)) @ V.T           # positive definite
+    d = np.sqrt(np.diag(C))
+    C = C / np.outer(d, d)
+    sq = np.sqrt(np.asarray(Q_DIAG, np.float64))
+    Q = np.outer(sq, sq) * C
+    R = np.diag(R_DIAG).copy()
+    for leg in range(4):
+        S = rng.uniform(-0.3, 0.3, size=(3, 3))
+        R[3 * leg:3 * leg + 3, 3 * leg:3 * leg + 3] += 1e-5 * (S @ S.T)
+    if cross_leg_r:
+        R[1, 7] = R[7, 1] = 3e-6
+    return 0.5 * (Q + Q.T), 0.5 * (R + R.T)
+
+
+def _cross_leg_weights(seed):
+    """The full Q of _full_weights and an R coupling every pair of legs: the reference's
+    diagonal scaled by a dense random correlation matrix (SPD, every cross-leg block non-zero)."""
+    from mpcqp.params import R_DIAG
+    Q, _ = _full_weights(seed)
+    rng = np.random.default_rng(seed + 1)
+    A = rng.standard_normal((12, 12))
+    C = A @ A.T / 12.0 + 0.5 * np.eye(12)
+    d = np.sqrt(np.diag(C))
+    C = C / np.outer(d, d)
+    sq = np.sqrt(np.asarray(R_DIAG, np.float64))
+    R = np.outer(sq, sq) * C
+    return Q, 0.5 * (R + R.T)

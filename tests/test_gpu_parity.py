@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import oracle_solution, rel_err_u0
+from helpers import _cross_leg_weights, _full_weights, oracle_solution, rel_err_u0   # noqa: F401 (the old names stay)
 
 TOL_U0 = 1e-4   # north_star: GRF within 1e-4 relative, norm-wise ||du0||_inf / ||u0*||_inf
 # the precision the engine actually delivers (dense classes ~5e-7, the interior-point
@@ -682,32 +682,6 @@ def test_stance_range_rejects_impossible_minimum_and_empty_ipm_robot():
         assert rel_err_u0(u0[b], x[:12]) < TOL_U0, b
 
 
-def _full_weights(seed, cross_leg_r=False):
-    """A symmetric positive-semidefinite Q coupling the state components (the reference's
-    diagonal scaled by a correlation matrix, |rho| <= 0.4: the weighting keeps the
-    reference's scale, so the float32 condensing of mpc.py:213-230 perturbs the optimum
-    as little as with the diagonal) and a leg-block R (or one with cross-leg terms)."""
-    from mpcqp.params import Q_DIAG, R_DIAG
-    rng = np.random.default_rng(seed)
-    C = np.eye(13)
-    for _ in range(12):
-        i, j = rng.choice(12, size=2, replace=False)   # state 12 (gravity) keeps weight 0
-        C[i, j] = C[j, i] = rng.uniform(-0.4, 0.4)
-    w, V = np.linalg.eigh(C)
-    C = V @ np.diag(np.maximum(w, 0.05)) @ V.T           # positive definite
-    d = np.sqrt(np.diag(C))
-    C = C / np.outer(d, d)
-    sq = np.sqrt(np.asarray(Q_DIAG, np.float64))
-    Q = np.outer(sq, sq) * C
-    R = np.diag(R_DIAG).copy()
-    for leg in range(4):
-        S = rng.uniform(-0.3, 0.3, size=(3, 3))
-        R[3 * leg:3 * leg + 3, 3 * leg:3 * leg + 3] += 1e-5 * (S @ S.T)
-    if cross_leg_r:
-        R[1, 7] = R[7, 1] = 3e-6
-    return 0.5 * (Q + Q.T), 0.5 * (R + R.T)
-
-
 @pytest.mark.parametrize("N", [10, 16, 20])
 def test_full_weights_match_oracle(N):
     """General (non-diagonal) Q and leg-block R (mpc.py:50,52 take full matrices,
@@ -811,21 +785,6 @@ def test_full_weights_cross_leg_r_and_validation():
     np.testing.assert_array_equal(kept[0], u0)
     assert int(eng.lib.mpcqp_set_weights(eng._ctx, np.ascontiguousarray(Q).ctypes.data, null)) == 0
     np.testing.assert_array_equal(_solve(eng, bt)[0], u0)
-
-
-def _cross_leg_weights(seed):
-    """The full Q of _full_weights and an R coupling every pair of legs: the reference's
-    diagonal scaled by a dense random correlation matrix (SPD, every cross-leg block non-zero)."""
-    from mpcqp.params import R_DIAG
-    Q, _ = _full_weights(seed)
-    rng = np.random.default_rng(seed + 1)
-    A = rng.standard_normal((12, 12))
-    C = A @ A.T / 12.0 + 0.5 * np.eye(12)
-    d = np.sqrt(np.diag(C))
-    C = C / np.outer(d, d)
-    sq = np.sqrt(np.asarray(R_DIAG, np.float64))
-    R = np.outer(sq, sq) * C
-    return Q, 0.5 * (R + R.T)
 
 
 @pytest.mark.parametrize("N", [16, 20, 24, 32])

@@ -160,10 +160,42 @@ def test_foot_weight_full_leg_block(foot):
         for r in range(6):
             if (live >> r) & 1:
                 want += d[r] * np.outer(rows[r], rows[r])
-        # cond(want) reaches ~1e7 (d_r / R): the adjugate inverse's forward error is ~cond x eps
+        # cond(want) reaches ~1e7 (d_r / R): the inverse's forward error is ~cond x eps
         inv = np.linalg.inv(want)
         err = np.abs(lib.weight(rows, live, d, rh) - inv).max() / np.abs(inv).max()
         assert err < 100 * np.finfo(float).eps * np.linalg.cond(want), (live, err)
+
+
+@pytest.mark.parametrize("full", [False, True])
+@pytest.mark.parametrize("big", [1e4, 1e6, 1e8])
+def test_foot_weight_one_nearly_active_row_on_a_tilted_cone(foot, big, full):
+    """The interior point's weight late in a solve: one row of a foot-step nearly active
+    (d = lambda / s = 1e4 .. 1e8 against Rh = 2e-5), the others far from it, on a tilted cone --
+    rows that are not exact in binary, so nothing cancels by luck.  W stays positive definite
+    (the Newton system convex) and within the same forward-error bound as above, 100 eps cond.
+    The adjugate inverse this replaced returned an indefinite W from d = 1e6 on (relative error
+    above 1), and the interior point stalled on every robot whose first polish did not verify."""
+    lib = foot[2]
+    rng = np.random.default_rng(5)
+    normal = np.array([0.1, 0.07, 0.99])
+    rows = _rows(0.37, normal / np.linalg.norm(normal))
+    for r_big in range(6):
+        live = 0b101111 if r_big != 4 else 0b111111
+        d = rng.uniform(1e-7, 1e-5, size=6)
+        d[r_big] = big
+        rh = _leg_block(rng) if full else 2e-5 * np.eye(3)
+        want = rh.copy()
+        for r in range(6):
+            if (live >> r) & 1:
+                want += d[r] * np.outer(rows[r], rows[r])
+        W = lib.weight(rows, live, d, rh)
+        inv = np.linalg.inv(want)
+        err = np.abs(W - inv).max() / np.abs(inv).max()
+        assert err < 100 * np.finfo(float).eps * np.linalg.cond(want), (r_big, err)
+        assert np.array_equal(W, W.T) and np.linalg.eigvalsh(W).min() > 0.0, (r_big, np.linalg.eigvalsh(W))
+        # along the nearly active row the weight is 1 / (d |a|^2) to first order: no force moves there
+        a = rows[r_big]
+        assert abs(a @ W @ a * big - 1.0) < 1e-2, (r_big, a @ W @ a * big)
 
 
 def test_foot_nullspace_full_leg_block(foot):
