@@ -42,6 +42,7 @@
 #include "mpcqp_predict_abi.h"
 #include "mpcqp_plant_abi.h"
 #include "mpcqp_certify_abi.h"
+#include "mpcqp_gait_abi.h"
 #include "mpcqp_solve_plan.h"
 
 namespace {
@@ -61,6 +62,7 @@ namespace {
 #include "mpcqp_predict.h"
 #include "mpcqp_certify.h"
 #include "mpcqp_plant.h"
+#include "mpcqp_gait.h"
 // the kernel headers' constants are those of include/mpcqp.h
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 static_assert(EST_STRIDE == MPCQP_EST_STRIDE, "estimator record stride");
@@ -71,6 +73,10 @@ static_assert(TER_ROBOT_STRIDE == MPCQP_ROBOT_STRIDE && TER_ROBOT_NORMAL == MPCQ
                   MPCQP_ROBOT_NORMAL + 3 <= MPCQP_ROBOT_STRIDE, "the normal's words of the robot record");
 static_assert(TER_SWING_STATE == MPCQP_TERRAIN_SWING_STATE && TER_ROOT_STATES == MPCQP_TERRAIN_ROOT_STATES, "flags");
 static_assert(TER_STATUS_OK == MPCQP_STATUS_OK && TER_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
+static_assert(SCHED_STRIDE == MPCQP_SCHED_STRIDE && GAIT_WORDS == MPCQP_GAIT_STRIDE && GAIT_LIB_MAX == MPCQP_GAIT_MAX &&
+                  GAIT_SWING_WORDS == MPCQP_SWING_STRIDE && GAIT_ADVANCE == MPCQP_GAIT_ADVANCE, "scheduler record and library");
+static_assert(GAIT_STATUS_OK == MPCQP_STATUS_OK && GAIT_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE &&
+                  GAIT_STATUS_UNSUPPORTED == MPCQP_STATUS_UNSUPPORTED, "status words");
 
 #include "mpcqp_classes.h"
 
@@ -159,6 +165,15 @@ struct mpcqp_ctx {
   double plant_ground_z = 0.0;
   bool plant_ground_set = false;
   double plant_contact_tol = 1e-4;
+  // the gait library (mpcqp_set_gaits): entries of GAIT_LIB_WORDS words, the record and its entry
+  // segment, on the host and on the device; and the scheduler's constants (mpcqp_set_gait_schedule)
+  int gait_count = 0;
+  int gait_lib[GAIT_LIB_MAX * GAIT_LIB_WORDS] = {};
+  int32_t* gait_dev = nullptr;
+  std::vector<int32_t*> gait_retired;   // earlier libraries (in-flight launches may read them)
+  int sched_min_hold = 0;
+  int sched_idle = -1, sched_move = -1, sched_dwell = 0;
+  double sched_v_go = 0.0, sched_v_stop = 0.0, sched_w_go = 0.0, sched_w_stop = 0.0;
   std::string err;
 };
 
@@ -1065,6 +1080,107 @@ int mpcqp_plant_reset(mpcqp_ctx* ctx, int32_t batch, const float* root_states, c
   return launched(ctx, "plant reset launch");
 }
 
+// ---- the gait scheduler (mpcqp_gait.h): what scripts/mujoco_aliengo.py:121-155 does by hand
+// between two runs (fresh Gait objects, iter_counter back at 0; gait.py:76-121), per robot and at
+// a tick that cuts no swing.  An invalid library or constant leaves the previous one in force.
+int mpcqp_set_gaits(mpcqp_ctx* ctx, int32_t count, const int32_t* records) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  int lib[GAIT_LIB_MAX * GAIT_LIB_WORDS] = {};
+  int which = -1;
+  switch (gait_library(count, records, lib, &which)) {
+    case 0: break;
+    case 1: return set_err(ctx, MPCQP_ERR_ARG, "gaits: count outside 1..16 or no records");
+    case 2:
+      return set_err(ctx, MPCQP_ERR_ARG, "gaits: record " + std::to_string(which) +
+                                             " needs 1 <= P <= 2048, 0 <= dur <= P and |off| <= 4 P");
+    default: return set_err(ctx, MPCQP_ERR_ARG, "gaits: record " + std::to_string(which) + " has no entry segment");
+  }
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  // into a fresh buffer; the context changes only once the upload succeeded
+  int32_t* nb = nullptr;
+  if (hipMalloc(&nb, sizeof(lib)) != hipSuccess) return set_err(ctx, MPCQP_ERR_ALLOC, "gaits: allocation failed");
+  if (hipMemcpy(nb, lib, sizeof(lib), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(nb);
+    return set_err(ctx, MPCQP_ERR_HIP, "gaits: upload failed");
+  }
+  // launches on any stream may still read the previous buffer: retired, not freed (640 bytes
+  // each), and released at mpcqp_destroy -- or, past kMaxRetired changes, after a synchronisation
+  if (ctx->gait_dev) {
+    if (ctx->gait_retired.size() >= kMaxRetired) {
+      if (hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(nb);
+        return set_err(ctx, MPCQP_ERR_HIP, "gaits: device sync failed");
+      }
+      for (int32_t* o : ctx->gait_retired) (void)hipFree(o);
+      ctx->gait_retired.clear();
+    }
+    ctx->gait_retired.push_back(ctx->gait_dev);
+  }
+  ctx->gait_dev = nb;
+  ctx->gait_count = count;
+  memcpy(ctx->gait_lib, lib, sizeof(lib));
+  if (ctx->sched_idle >= count || ctx->sched_move >= count) ctx->sched_idle = ctx->sched_move = -1;
+  return MPCQP_OK;
+}
+
+int mpcqp_set_gait_schedule(mpcqp_ctx* ctx, int32_t min_hold, int32_t idle_gait, int32_t move_gait, double v_go,
+                            double v_stop, double w_go, double w_stop, int32_t dwell) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (min_hold < 0) return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: min_hold < 0");
+  if (!all_finite({v_go, v_stop, w_go, w_stop})) return set_err(ctx, MPCQP_ERR_ARG, "non-finite gait schedule constant");
+  if (idle_gait != -1) {
+    if (idle_gait < 0 || idle_gait >= ctx->gait_count || move_gait < 0 || move_gait >= ctx->gait_count)
+      return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: idle_gait or move_gait outside the library");
+    if (v_stop < 0.0 || v_stop > v_go || w_stop < 0.0 || w_stop > w_go)
+      return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: needs 0 <= v_stop <= v_go and 0 <= w_stop <= w_go");
+    if (dwell < 0) return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: dwell < 0");
+  }
+  ctx->sched_min_hold = min_hold;
+  ctx->sched_idle = idle_gait;
+  ctx->sched_move = idle_gait == -1 ? -1 : move_gait;
+  ctx->sched_v_go = v_go, ctx->sched_v_stop = v_stop, ctx->sched_w_go = w_go, ctx->sched_w_stop = w_stop;
+  ctx->sched_dwell = dwell;
+  return MPCQP_OK;
+}
+
+int mpcqp_gait_schedule(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t iterations_between_mpc,
+                        const int32_t* want, const double* vel_body_des, const double* yaw_rate_des,
+                        int32_t* sched_state, int32_t* gait, int32_t* tick, double* swing_mem, int32_t* iteration,
+                        int32_t* switched, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (flags & ~MPCQP_GAIT_ADVANCE) return set_err(ctx, MPCQP_ERR_ARG, "unknown gait schedule flags");
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: batch < 0");
+  if (iterations_between_mpc < 1) return set_err(ctx, MPCQP_ERR_ARG, "iterations_between_mpc < 1");
+  if (!sched_state || !gait || !tick) return set_err(ctx, MPCQP_ERR_ARG, "null gait schedule state pointer");
+  if (ctx->gait_count < 1) return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: no library set (mpcqp_set_gaits)");
+  if (!want && ctx->sched_idle < 0)
+    return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: no want and the automatic choice is disabled");
+  if (!want && (!vel_body_des || !yaw_rate_des))
+    return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: the automatic choice needs vel_body_des and yaw_rate_des");
+  if (int rc = aligned16(ctx, sched_state, "sched_state")) return rc;
+  if (int rc = aligned16(ctx, swing_mem, "swing_mem")) return rc;
+  for (int i = 0; i < ctx->gait_count; ++i)
+    if ((long long)ctx->gait_lib[GAIT_LIB_WORDS * i + GAIT_WORDS] * iterations_between_mpc > GAIT_INT_MAX)
+      return set_err(ctx, MPCQP_ERR_ARG, "gait schedule: an entry tick is beyond INT32_MAX");
+  if (batch == 0) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  GaitParams gp;
+  gp.count = ctx->gait_count;
+  gp.ibm = iterations_between_mpc;
+  gp.flags = flags;
+  gp.min_hold = ctx->sched_min_hold;
+  gp.idle = ctx->sched_idle, gp.move = ctx->sched_move;
+  gp.dwell = ctx->sched_dwell;
+  gp.v_go2 = ctx->sched_v_go * ctx->sched_v_go, gp.v_stop2 = ctx->sched_v_stop * ctx->sched_v_stop;
+  gp.w_go = ctx->sched_w_go, gp.w_stop = ctx->sched_w_stop;
+  hipLaunchKernelGGL(mpcqp_gait_kernel, dim3((batch + kGaitThreads - 1) / kGaitThreads), dim3(kGaitThreads), 0,
+                     (hipStream_t)stream, gp, (int)batch, (const int32_t*)ctx->gait_dev, want, vel_body_des,
+                     yaw_rate_des, sched_state, gait, tick, swing_mem, iteration, switched, status);
+  return launched(ctx, "gait schedule launch");
+}
+
 int mpcqp_destroy(mpcqp_ctx* ctx) {
   if (ctx) {
     DeviceScope dev(ctx->device);
@@ -1075,6 +1191,8 @@ int mpcqp_destroy(mpcqp_ctx* ctx) {
     if (ctx->prio_tab) (void)hipFree(ctx->prio_tab);
     if (ctx->wdev) (void)hipFree(ctx->wdev);
     for (double* o : ctx->retired) (void)hipFree(o);
+    if (ctx->gait_dev) (void)hipFree(ctx->gait_dev);
+    for (int32_t* o : ctx->gait_retired) (void)hipFree(o);
   }
   delete ctx;
   return MPCQP_OK;

@@ -43,6 +43,9 @@ PLANT_STRIDE = 48          # MPCQP_PLANT_STRIDE (mpcqp_plant_abi.h): float64 pla
 PLANT_MAX_SUBSTEPS = 16    # MPCQP_PLANT_MAX_SUBSTEPS (mpcqp_plant_abi.h)
 PREDICT_REPORT = 4         # MPCQP_PREDICT_REPORT (mpcqp_predict_abi.h): float64 report per robot (cost, cost_free, cone margin, swing residual)
 
+GAIT_MAX = 16              # MPCQP_GAIT_MAX (mpcqp_gait_abi.h): entries of the gait library
+SCHED_STRIDE = 8           # MPCQP_SCHED_STRIDE (mpcqp_gait_abi.h): int32 scheduler record per robot (current, pending, since, switches, calm, last tick)
+GAIT_ADVANCE = 1           # MPCQP_GAIT_ADVANCE (mpcqp_gait_abi.h): advance tick and since before deciding
 CERTIFY_REPORT = 4         # MPCQP_CERTIFY_REPORT (mpcqp_certify_abi.h): float64 report per robot (objective, gap, lower bound, worst foot-step term)
 
 
@@ -111,6 +114,13 @@ PLANT_SIGNATURES = {
 CERTIFY_SIGNATURES = {
     "mpcqp_certify": (_int, [_vp, _i32, _i32] + [_vp] * 10),
 }
+# The companion header include/mpcqp_gait_abi.h, one row per function it declares
+# (tests/test_gait.py holds each row to its declaration, position by position).
+GAIT_SIGNATURES = {
+    "mpcqp_set_gaits": (_int, [_vp, _i32, _vp]),
+    "mpcqp_set_gait_schedule": (_int, [_vp, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32]),
+    "mpcqp_gait_schedule": (_int, [_vp, _i32, _i32, _i32] + [_vp] * 11),
+}
 
 
 class MpcqpError(RuntimeError):
@@ -130,7 +140,7 @@ def load():
                          "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **PREDICT_SIGNATURES, **PLANT_SIGNATURES,
-                                       **CERTIFY_SIGNATURES}.items():
+                                       **CERTIFY_SIGNATURES, **GAIT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mpcqp_abi_version() != ABI_VERSION:
