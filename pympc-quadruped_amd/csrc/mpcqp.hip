@@ -43,6 +43,7 @@
 #include "mpcqp_plant_abi.h"
 #include "mpcqp_certify_abi.h"
 #include "mpcqp_gait_abi.h"
+#include "mpcqp_disturb_abi.h"
 #include "mpcqp_solve_plan.h"
 
 namespace {
@@ -63,6 +64,7 @@ namespace {
 #include "mpcqp_certify.h"
 #include "mpcqp_plant.h"
 #include "mpcqp_gait.h"
+#include "mpcqp_sensors.h"
 // the kernel headers' constants are those of include/mpcqp.h
 static_assert(MPCQP_KIN_STRIDE == KIN_STRIDE, "geometry record: include/mpcqp.h and mpcqp_kin_leg.h agree");
 static_assert(EST_STRIDE == MPCQP_EST_STRIDE, "estimator record stride");
@@ -174,6 +176,12 @@ struct mpcqp_ctx {
   int sched_min_hold = 0;
   int sched_idle = -1, sched_move = -1, sched_dwell = 0;
   double sched_v_go = 0.0, sched_v_stop = 0.0, sched_w_go = 0.0, sched_w_stop = 0.0;
+  // the sensor model's constants (mpcqp_set_sensors): all zero, the stage is the identity on values
+  uint64_t sense_seed = 0;
+  double sense_sigma_gyro = 0.0, sense_sigma_accel = 0.0, sense_walk_gyro = 0.0, sense_walk_accel = 0.0;
+  double sense_bias0_gyro = 0.0, sense_bias0_accel = 0.0, sense_sigma_q = 0.0, sense_sigma_qd = 0.0, sense_q_lsb = 0.0;
+  int sense_touch_lag = 0;
+  double sense_p_drop = 0.0;
   std::string err;
 };
 
@@ -1179,6 +1187,74 @@ int mpcqp_gait_schedule(mpcqp_ctx* ctx, int32_t batch, int32_t flags, int32_t it
                      (hipStream_t)stream, gp, (int)batch, (const int32_t*)ctx->gait_dev, want, vel_body_des,
                      yaw_rate_des, sched_state, gait, tick, swing_mem, iteration, switched, status);
   return launched(ctx, "gait schedule launch");
+}
+
+// ---- the sensor model and the push (mpcqp_sensors.h): the reference's scripts read a simulator's
+// sensors as they come and never disturb the robot (gym.simulate, sim.step()).  An invalid
+// constant leaves the previous set in force.
+int mpcqp_set_sensors(mpcqp_ctx* ctx, uint64_t seed, double sigma_gyro, double sigma_accel, double walk_gyro,
+                      double walk_accel, double bias0_gyro, double bias0_accel, double sigma_q, double sigma_qd,
+                      double q_lsb, int32_t touch_lag, double p_drop) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (!all_finite({sigma_gyro, sigma_accel, walk_gyro, walk_accel, bias0_gyro, bias0_accel, sigma_q, sigma_qd, q_lsb,
+                   p_drop}))
+    return set_err(ctx, MPCQP_ERR_ARG, "non-finite sensor constant");
+  for (double v : {sigma_gyro, sigma_accel, walk_gyro, walk_accel, bias0_gyro, bias0_accel, sigma_q, sigma_qd, q_lsb})
+    if (v < 0.0) return set_err(ctx, MPCQP_ERR_ARG, "negative sensor constant");
+  if (touch_lag < 0 || touch_lag > SENSE_MAX_LAG) return set_err(ctx, MPCQP_ERR_ARG, "sensors: touch_lag outside 0..31");
+  if (!(p_drop >= 0.0 && p_drop < 1.0)) return set_err(ctx, MPCQP_ERR_ARG, "sensors: p_drop outside [0, 1)");
+  ctx->sense_seed = seed;
+  ctx->sense_sigma_gyro = sigma_gyro, ctx->sense_sigma_accel = sigma_accel;
+  ctx->sense_walk_gyro = walk_gyro, ctx->sense_walk_accel = walk_accel;
+  ctx->sense_bias0_gyro = bias0_gyro, ctx->sense_bias0_accel = bias0_accel;
+  ctx->sense_sigma_q = sigma_q, ctx->sense_sigma_qd = sigma_qd, ctx->sense_q_lsb = q_lsb;
+  ctx->sense_touch_lag = touch_lag;
+  ctx->sense_p_drop = p_drop;
+  return MPCQP_OK;
+}
+
+int mpcqp_sensors(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* gyro, const float* accel,
+                  const float* dof_states, const float* touch, const float* scale, double* sense_state,
+                  float* gyro_m, float* accel_m, float* dof_states_m, float* touch_m, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (flags != 0) return set_err(ctx, MPCQP_ERR_ARG, "unknown sensors flags");
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "sensors: batch < 0");
+  if (!sense_state) return set_err(ctx, MPCQP_ERR_ARG, "null sense_state pointer");
+  if (!gyro != !gyro_m || !accel != !accel_m || !dof_states != !dof_states_m || !touch != !touch_m)
+    return set_err(ctx, MPCQP_ERR_ARG, "sensors: an input and its output are given together or not at all");
+  if (int rc = aligned16(ctx, sense_state, "sense_state")) return rc;
+  if (((uintptr_t)dof_states | (uintptr_t)dof_states_m) & 7)
+    return set_err(ctx, MPCQP_ERR_ARG, "sensors: dof_states or dof_states_m is not 8-byte aligned");
+  if (batch == 0) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  SenseParams sp;
+  sp.key0 = (uint32_t)ctx->sense_seed, sp.key1 = (uint32_t)(ctx->sense_seed >> 32);
+  sp.sigma_gyro = ctx->sense_sigma_gyro, sp.sigma_accel = ctx->sense_sigma_accel;
+  sp.walk_gyro = ctx->sense_walk_gyro, sp.walk_accel = ctx->sense_walk_accel;
+  sp.bias0_gyro = ctx->sense_bias0_gyro, sp.bias0_accel = ctx->sense_bias0_accel;
+  sp.sigma_q = ctx->sense_sigma_q, sp.sigma_qd = ctx->sense_sigma_qd, sp.q_lsb = ctx->sense_q_lsb;
+  sp.sqrt_dt = std::sqrt(ctx->dt_control);
+  sp.drop = (uint32_t)std::floor(ctx->sense_p_drop * 4294967296.0);
+  sp.touch_lag = ctx->sense_touch_lag;
+  hipLaunchKernelGGL(mpcqp_sensors_kernel, dim3((batch + kSenseRobots - 1) / kSenseRobots), dim3(kSenseThreads), 0,
+                     (hipStream_t)stream, sp, (int)batch, gyro, accel, dof_states, touch, scale, sense_state, gyro_m,
+                     accel_m, dof_states_m, touch_m, status);
+  return launched(ctx, "sensors launch");
+}
+
+int mpcqp_push(mpcqp_ctx* ctx, int32_t batch, const float* impulse, const float* point, const float* robot,
+               double* plant_state, int32_t* status, void* stream) {
+  if (!ctx) return MPCQP_ERR_ARG;
+  if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "push: batch < 0");
+  if (!impulse || !robot || !plant_state) return set_err(ctx, MPCQP_ERR_ARG, "null push input/state pointer");
+  if (int rc = aligned16(ctx, plant_state, "plant_state")) return rc;
+  if (batch == 0) return MPCQP_OK;
+  DeviceScope dev(ctx->device);
+  if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
+  hipLaunchKernelGGL(mpcqp_push_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, (int)batch, impulse,
+                     point, robot, plant_state, status);
+  return launched(ctx, "push launch");
 }
 
 int mpcqp_destroy(mpcqp_ctx* ctx) {

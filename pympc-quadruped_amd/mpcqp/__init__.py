@@ -6,7 +6,7 @@ Drop-in for the formulate-and-solve hot path of yinghansun/pympc-quadruped
 from .params import (DT_MPC, GAITS, GRAVITY, LEG_GEOMETRY, MU, Q_DIAG, R_DIAG, ROBOT_PRESETS, ROBOT_STRIDE,
                      leg_geometry_from_urdf, pack_leg_geometry, pack_robot, robot_from_config)
 
-__all__ = ["LinearMpc", "SolveResult", "PredictResult", "CertifyResult", "BatchedTerrain", "BatchedPlant", "BatchedGaitScheduler", "DT_MPC", "GAITS", "GRAVITY", "LEG_GEOMETRY", "MU", "Q_DIAG", "R_DIAG",
+__all__ = ["LinearMpc", "SolveResult", "PredictResult", "CertifyResult", "BatchedTerrain", "BatchedPlant", "BatchedGaitScheduler", "BatchedSensors", "SENSOR_PRESETS", "DT_MPC", "GAITS", "GRAVITY", "LEG_GEOMETRY", "MU", "Q_DIAG", "R_DIAG",
            "ROBOT_PRESETS", "ROBOT_STRIDE", "leg_geometry_from_urdf", "pack_leg_geometry", "pack_robot",
            "robot_from_config"]
 
@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == "BatchedGaitScheduler":
         from .gait import BatchedGaitScheduler
         return BatchedGaitScheduler
+    if name in ("BatchedSensors", "SENSOR_PRESETS"):
+        from . import sensors
+        return getattr(sensors, name)
     raise AttributeError(name)

@@ -46,6 +46,7 @@ PREDICT_REPORT = 4         # MPCQP_PREDICT_REPORT (mpcqp_predict_abi.h): float64
 GAIT_MAX = 16              # MPCQP_GAIT_MAX (mpcqp_gait_abi.h): entries of the gait library
 SCHED_STRIDE = 8           # MPCQP_SCHED_STRIDE (mpcqp_gait_abi.h): int32 scheduler record per robot (current, pending, since, switches, calm, last tick)
 GAIT_ADVANCE = 1           # MPCQP_GAIT_ADVANCE (mpcqp_gait_abi.h): advance tick and since before deciding
+SENSE_STRIDE = 16          # MPCQP_SENSE_STRIDE (mpcqp_disturb_abi.h): float64 sensor record per robot (gyro bias, accel bias, initialised, count, id, touch histories)
 CERTIFY_REPORT = 4         # MPCQP_CERTIFY_REPORT (mpcqp_certify_abi.h): float64 report per robot (objective, gap, lower bound, worst foot-step term)
 
 
@@ -60,7 +61,7 @@ class MpcqpParams(ctypes.Structure):
     ]
 
 
-_vp, _i32, _int, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int, ctypes.c_double
+_vp, _i32, _int, _f64, _u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_uint64
 _params_p = ctypes.POINTER(MpcqpParams)
 
 # The ABI, one row per function declared in include/mpcqp.h: symbol -> (restype, argtypes).
@@ -121,6 +122,13 @@ GAIT_SIGNATURES = {
     "mpcqp_set_gait_schedule": (_int, [_vp, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32]),
     "mpcqp_gait_schedule": (_int, [_vp, _i32, _i32, _i32] + [_vp] * 11),
 }
+# The companion header include/mpcqp_disturb_abi.h, one row per function it declares
+# (tests/test_disturb.py holds each row to its declaration, position by position).
+DISTURB_SIGNATURES = {
+    "mpcqp_sensors": (_int, [_vp, _i32, _i32] + [_vp] * 12),
+    "mpcqp_set_sensors": (_int, [_vp, _u64] + [_f64] * 9 + [_i32, _f64]),
+    "mpcqp_push": (_int, [_vp, _i32] + [_vp] * 6),
+}
 
 
 class MpcqpError(RuntimeError):
@@ -140,7 +148,8 @@ def load():
                          "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **PREDICT_SIGNATURES, **PLANT_SIGNATURES,
-                                       **CERTIFY_SIGNATURES, **GAIT_SIGNATURES}.items():
+                                       **CERTIFY_SIGNATURES, **GAIT_SIGNATURES,
+                                       **DISTURB_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mpcqp_abi_version() != ABI_VERSION:

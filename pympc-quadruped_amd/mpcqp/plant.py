@@ -94,6 +94,7 @@ class BatchedPlant:
         self.accel = torch.zeros((B, 3), **f32)
         self.touch = torch.zeros((B, 4), **f32)
         self.status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.push_status = torch.zeros((B,), dtype=torch.int32, device=dev)
         self._bound = {}
 
     def set_constants(self, foot_mass=None, substeps=None, ground_z=None, contact_tol=None):
@@ -185,6 +186,41 @@ class BatchedPlant:
                 launch = self._bound[key] = self.bind_step(tau)
         launch(torch.cuda.current_stream(self.device) if stream is None else stream)
         return self.root, self.dofs
+
+    def bind_push(self, impulse, point=None):
+        """``push`` with its checks made and its device pointers resolved once: returns
+        ``launch(stream)`` (see ``bind_step``), e.g. for capture into a HIP graph; the caller
+        writes the impulses into the bound tensor between two launches."""
+        for name, t in (("impulse", impulse), ("point", point)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                                      and t.device == self.device and t.numel() == self.B * 3):
+                what = f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', 'the host')}"
+                raise ValueError(f"plant: {name} must be a contiguous float32 tensor of shape [{self.B}, 3] on "
+                                 f"{self.device}, got {what}")
+        lib, ctx = self.lib, self._ctx
+        args = (ctx, self.B, _ptr(impulse), _ptr(point), _ptr(self.robot), _ptr(self.state), _ptr(self.push_status))
+
+        def launch(stream):
+            _lib.check(ctx, lib.mpcqp_push(*args, ctypes.c_void_p(stream.cuda_stream)), "mpcqp_push")
+        launch.buffers = (impulse, point, self.robot, self.state)
+        return launch
+
+    def push(self, impulse, point=None, stream=None):
+        """An impulse on every robot's record, one launch (mpcqp_push): ``impulse`` [B,3] or [3]
+        in the world frame, N s, acting at ``point`` [B,3] or [3] in the body frame from the
+        centre of mass (None: at the centre of mass): v += J / m, w += I_w^-1 ((Rq r) x J).  Feet
+        and contacts are not touched (a pinned foot stays pinned) and a zero impulse leaves the
+        record bit by bit.  A force F over one tick is the impulse F dt_control, given every
+        tick; ``accel`` does not see an impulse.  Fills ``push_status`` [B] int32: STATUS_NONFINITE
+        for a robot with a non-finite impulse, point, record or result, which is left untouched.
+        Anything but a float32 device tensor [B,3] is converted on each call."""
+        def dev(t):
+            if t is None or (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                             and t.device == self.device and t.numel() == self.B * 3):
+                return t
+            t = torch.as_tensor(t, dtype=torch.float32).to(self.device)
+            return (t.expand(self.B, 3) if t.dim() == 1 else t.reshape(self.B, 3)).contiguous()
+        self.bind_push(dev(impulse), dev(point))(torch.cuda.current_stream(self.device) if stream is None else stream)
 
     # ---- views of the records
     @property
