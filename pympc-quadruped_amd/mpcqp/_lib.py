@@ -1,4 +1,4 @@
-"""ctypes binding of libmpcqp.so (include/mpcqp.h).
+"""ctypes binding of libmpcqp.so (include/mpcqp.h and its companion headers).
 
 The shared library is built in-tree (``__graft_entry__.build()`` or
 ``python -m mpcqp.build``) next to this file.  There is deliberately no
@@ -64,71 +64,66 @@ class MpcqpParams(ctypes.Structure):
 _vp, _i32, _int, _f64, _u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int, ctypes.c_double, ctypes.c_uint64
 _params_p = ctypes.POINTER(MpcqpParams)
 
-# The ABI, one row per function declared in include/mpcqp.h: symbol -> (restype, argtypes).
-# The context, the stream and every device or host array travel as void pointers
-# (tests/test_abi.py holds each row to its declaration, position by position).
-SIGNATURES = {
-    "mpcqp_abi_version": (_i32, []),
-    "mpcqp_default_params": (None, [_params_p, _i32]),
-    "mpcqp_create": (_int, [_params_p, _i32, ctypes.POINTER(_vp)]),
-    "mpcqp_solve": (_int, [_vp, _i32] + [_vp] * 10),
-    "mpcqp_set_stance_hint": (_int, [_vp, _i32]),
-    "mpcqp_set_stance_range": (_int, [_vp, _i32, _i32]),
-    "mpcqp_set_order": (_int, [_vp, _i32]),
-    "mpcqp_set_weights": (_int, [_vp, _vp, _vp]),
-    "mpcqp_set_warm_start": (_int, [_vp, _vp, _i32]),
-    "mpcqp_destroy": (_int, [_vp]),
-    "mpcqp_last_error": (ctypes.c_char_p, [_vp]),
-    "mpcqp_plan": (_int, [_vp, _i32, _i32] + [_vp] * 15),
-    "mpcqp_plan_root_states": (_int, [_vp, _i32, _i32] + [_vp] * 11),
-    "mpcqp_set_planner": (_int, [_vp, _f64, _f64, _f64]),
-    "mpcqp_stance_torques": (_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "mpcqp_leg_torques": (_int, [_vp, _i32, _i32, _vp, _i32] + [_vp] * 19),
-    "mpcqp_leg_torques_root_states": (_int, [_vp, _i32, _i32, _vp, _i32] + [_vp] * 16),
-    "mpcqp_set_swing": (_int, [_vp, _f64, _vp, _vp, _f64, _f64]),
-    "mpcqp_kinematics": (_int, [_vp, _i32, _i32] + [_vp] * 15),
-    "mpcqp_kinematics_root_states": (_int, [_vp, _i32, _i32] + [_vp] * 10),
-    "mpcqp_step": (_int, [_vp, _i32, _i32, _i32, _vp, _i32] + [_vp] * 27),
-    "mpcqp_estimate": (_int, [_vp, _i32, _i32] + [_vp] * 12),
-    "mpcqp_set_estimator": (_int, [_vp] + [_f64] * 11),
-    "mpcqp_attitude": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32] + [_vp] * 8),
-    "mpcqp_set_attitude": (_int, [_vp] + [_f64] * 6),
-    "mpcqp_terrain": (_int, [_vp, _i32, _i32] + [_vp] * 10),
-    "mpcqp_set_terrain": (_int, [_vp] + [_f64] * 4),
-    "mpcqp_set_ground": (_int, [_vp, _vp, _i32]),
+# The ABI, one row per function the headers under include/ declare: header -> symbol ->
+# (restype, argtypes).  The context, the stream and every device or host array travel as void
+# pointers (tests/test_abi.py holds each row to its declaration, position by position, and
+# each symbol to one header).  A new stage is a new header and its rows here.
+ABI = {
+    "mpcqp.h": {
+        "mpcqp_abi_version": (_i32, []),
+        "mpcqp_default_params": (None, [_params_p, _i32]),
+        "mpcqp_create": (_int, [_params_p, _i32, ctypes.POINTER(_vp)]),
+        "mpcqp_solve": (_int, [_vp, _i32] + [_vp] * 10),
+        "mpcqp_set_stance_hint": (_int, [_vp, _i32]),
+        "mpcqp_set_stance_range": (_int, [_vp, _i32, _i32]),
+        "mpcqp_set_order": (_int, [_vp, _i32]),
+        "mpcqp_set_weights": (_int, [_vp, _vp, _vp]),
+        "mpcqp_set_warm_start": (_int, [_vp, _vp, _i32]),
+        "mpcqp_destroy": (_int, [_vp]),
+        "mpcqp_last_error": (ctypes.c_char_p, [_vp]),
+        "mpcqp_plan": (_int, [_vp, _i32, _i32] + [_vp] * 15),
+        "mpcqp_plan_root_states": (_int, [_vp, _i32, _i32] + [_vp] * 11),
+        "mpcqp_set_planner": (_int, [_vp, _f64, _f64, _f64]),
+        "mpcqp_stance_torques": (_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+        "mpcqp_leg_torques": (_int, [_vp, _i32, _i32, _vp, _i32] + [_vp] * 19),
+        "mpcqp_leg_torques_root_states": (_int, [_vp, _i32, _i32, _vp, _i32] + [_vp] * 16),
+        "mpcqp_set_swing": (_int, [_vp, _f64, _vp, _vp, _f64, _f64]),
+        "mpcqp_kinematics": (_int, [_vp, _i32, _i32] + [_vp] * 15),
+        "mpcqp_kinematics_root_states": (_int, [_vp, _i32, _i32] + [_vp] * 10),
+        "mpcqp_step": (_int, [_vp, _i32, _i32, _i32, _vp, _i32] + [_vp] * 27),
+        "mpcqp_estimate": (_int, [_vp, _i32, _i32] + [_vp] * 12),
+        "mpcqp_set_estimator": (_int, [_vp] + [_f64] * 11),
+        "mpcqp_attitude": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32] + [_vp] * 8),
+        "mpcqp_set_attitude": (_int, [_vp] + [_f64] * 6),
+        "mpcqp_terrain": (_int, [_vp, _i32, _i32] + [_vp] * 10),
+        "mpcqp_set_terrain": (_int, [_vp] + [_f64] * 4),
+        "mpcqp_set_ground": (_int, [_vp, _vp, _i32]),
+    },
+    "mpcqp_predict_abi.h": {
+        "mpcqp_predict": (_int, [_vp, _i32, _i32] + [_vp] * 10),
+    },
+    "mpcqp_plant_abi.h": {
+        "mpcqp_plant": (_int, [_vp, _i32, _i32] + [_vp] * 12),
+        "mpcqp_plant_reset": (_int, [_vp, _i32] + [_vp] * 6),
+        "mpcqp_set_plant": (_int, [_vp, _f64, _i32, _f64, _f64]),
+    },
+    "mpcqp_certify_abi.h": {
+        "mpcqp_certify": (_int, [_vp, _i32, _i32] + [_vp] * 10),
+    },
+    "mpcqp_gait_abi.h": {
+        "mpcqp_set_gaits": (_int, [_vp, _i32, _vp]),
+        "mpcqp_set_gait_schedule": (_int, [_vp, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32]),
+        "mpcqp_gait_schedule": (_int, [_vp, _i32, _i32, _i32] + [_vp] * 11),
+    },
+    "mpcqp_disturb_abi.h": {
+        "mpcqp_sensors": (_int, [_vp, _i32, _i32] + [_vp] * 12),
+        "mpcqp_set_sensors": (_int, [_vp, _u64] + [_f64] * 9 + [_i32, _f64]),
+        "mpcqp_push": (_int, [_vp, _i32] + [_vp] * 6),
+    },
 }
-EXPORTED_SYMBOLS = tuple(SIGNATURES)   # every symbol declared in include/mpcqp.h
-# The companion header include/mpcqp_predict_abi.h, one row per function it declares
-# (tests/test_predict.py holds the row to its declaration, position by position).
-PREDICT_SIGNATURES = {
-    "mpcqp_predict": (_int, [_vp, _i32, _i32] + [_vp] * 10),
-}
-# The companion header include/mpcqp_plant_abi.h, one row per function it declares
-# (tests/test_plant.py holds each row to its declaration, position by position).
-PLANT_SIGNATURES = {
-    "mpcqp_plant": (_int, [_vp, _i32, _i32] + [_vp] * 12),
-    "mpcqp_plant_reset": (_int, [_vp, _i32] + [_vp] * 6),
-    "mpcqp_set_plant": (_int, [_vp, _f64, _i32, _f64, _f64]),
-}
-# The companion header include/mpcqp_certify_abi.h, one row per function it declares
-# (tests/test_certify.py holds the row to its declaration, position by position).
-CERTIFY_SIGNATURES = {
-    "mpcqp_certify": (_int, [_vp, _i32, _i32] + [_vp] * 10),
-}
-# The companion header include/mpcqp_gait_abi.h, one row per function it declares
-# (tests/test_gait.py holds each row to its declaration, position by position).
-GAIT_SIGNATURES = {
-    "mpcqp_set_gaits": (_int, [_vp, _i32, _vp]),
-    "mpcqp_set_gait_schedule": (_int, [_vp, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32]),
-    "mpcqp_gait_schedule": (_int, [_vp, _i32, _i32, _i32] + [_vp] * 11),
-}
-# The companion header include/mpcqp_disturb_abi.h, one row per function it declares
-# (tests/test_disturb.py holds each row to its declaration, position by position).
-DISTURB_SIGNATURES = {
-    "mpcqp_sensors": (_int, [_vp, _i32, _i32] + [_vp] * 12),
-    "mpcqp_set_sensors": (_int, [_vp, _u64] + [_f64] * 9 + [_i32, _f64]),
-    "mpcqp_push": (_int, [_vp, _i32] + [_vp] * 6),
-}
+# every row, flat: what load() applies
+SIGNATURES = {name: row for rows in ABI.values() for name, row in rows.items()}
+EXPORTED_SYMBOLS = tuple(ABI["mpcqp.h"])   # every symbol declared in include/mpcqp.h
 
 
 class MpcqpError(RuntimeError):
@@ -147,9 +142,7 @@ def load():
         raise MpcqpError(f"{LIB_PATH} not built: run __graft_entry__.build() "
                          "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **PREDICT_SIGNATURES, **PLANT_SIGNATURES,
-                                       **CERTIFY_SIGNATURES, **GAIT_SIGNATURES,
-                                       **DISTURB_SIGNATURES}.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.mpcqp_abi_version() != ABI_VERSION:

@@ -1,27 +1,33 @@
-"""Shared test helpers: oracle solutions for synthetic batches (CPU, float64), the symbols
-include/mpcqp.h declares, the prototypes of a header, and the full (non-diagonal) weights the
-parity and the interior-point edge tests share."""
+"""Shared test helpers: oracle solutions for synthetic batches (CPU, float64), the prototypes
+of a header under include/, one host build per (shim, flags), one device-only compile for the
+kernels' resource remarks, the device copies of the GPU tests, and the full (non-diagonal)
+weights the parity and the interior-point edge tests share."""
+import ctypes
 import os
 import re
+import shutil
+import subprocess
+import tempfile
 
 import numpy as np
 
 from oracle import formulation as F
 from oracle import qp as QP
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mpcqp.h")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
+DEV = "cuda:0"
+
+_tmp = None
+_host_builds = {}
+_kernel_usage = None
 
 
-def _declared():
-    """The name of every function include/mpcqp.h declares."""
-    src = open(HEADER).read()
-    return set(re.findall(r"^\s*(?:[a-zA-Z_][\w\s\*]*?)\b(mpcqp_\w+)\s*\(", src, re.M))
-
-
-def _prototypes(header):
-    """{name: (return type, [parameter types])} of the header at that path, comments removed; a
-    type is the declaration's text less the parameter's name, "T*" for every pointer."""
-    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(header).read(), flags=re.S)
+def _prototypes(header="mpcqp.h"):
+    """{name: (return type, [parameter types])} of that header under include/, comments removed;
+    a type is the declaration's text less the parameter's name, "T*" for every pointer."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
     out = {}
     for ret, name, params in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(mpcqp_\w+)\s*\(([^)]*)\)\s*;", src, re.M):
         kinds = []
@@ -34,11 +40,73 @@ def _prototypes(header):
     return out
 
 
-def _int_prototypes(header):
-    """{name: [parameter types]} of a companion header, every function of which returns int."""
-    protos = _prototypes(header)
-    assert all(ret == "int" for ret, _ in protos.values()), protos
-    return {name: kinds for name, (_, kinds) in protos.items()}
+def _declared():
+    """The name of every function include/mpcqp.h declares."""
+    return set(_prototypes())
+
+
+def _tmpdir(name):
+    """A fresh folder for a build's files, removed with the rest when the process ends."""
+    global _tmp
+    if _tmp is None:
+        _tmp = tempfile.TemporaryDirectory(prefix="mpcqp_tests_")
+    return tempfile.mkdtemp(prefix=name + "_", dir=_tmp.name)
+
+
+def host_build(shim_text, flags=("-O2", "-ffp-contract=off"), name="shim"):
+    """The shim compiled for the host with g++ <flags> -shared -fPIC -I csrc and loaded: one
+    ctypes.CDLL per (shim text, flags) for the life of the process, so a module that imports
+    another's fixture reuses its build."""
+    key = (shim_text, tuple(flags))
+    if key not in _host_builds:
+        d = _tmpdir(name)
+        src, so = os.path.join(d, "shim.cpp"), os.path.join(d, f"lib{name}.so")
+        with open(src, "w") as fh:
+            fh.write(shim_text)
+        subprocess.run(["g++", *flags, "-shared", "-fPIC", "-I", CSRC, "-o", so, src], check=True)
+        _host_builds[key] = ctypes.CDLL(so)
+    return _host_builds[key]
+
+
+def _vp(a):
+    """A numpy array (or None) as the void pointer a host-compiled shim takes."""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def kernel_usage():
+    """{mangled kernel name: {remark: value}} of one device-only compile of the library for
+    gfx950 per process; skips the calling test where hipcc is absent."""
+    global _kernel_usage
+    if _kernel_usage is not None:
+        return _kernel_usage
+    import pytest
+    from mpcqp import build as B
+    if not os.path.exists(B.HIPCC) and not shutil.which("hipcc"):
+        pytest.skip("hipcc not installed")
+    cmd = [B.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-c",
+           "-I" + os.path.join(B.ROOT, "include"), "-o", os.path.join(_tmpdir("build"), "dev.o"), B.SRC,
+           "-Rpass-analysis=kernel-resource-usage"]
+    out = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
+    usage = {}
+    name = None
+    for line in out.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
+        if m and name:
+            usage[name][m.group(1).strip()] = int(m.group(2))
+    _kernel_usage = usage
+    return usage
+
+
+def _dev(a, dtype=None):
+    """A contiguous copy of an array on the device, converted there when a dtype is given."""
+    import torch
+    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
+    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def oracle_solution(batch, b, horizon, Q=F.Q_DIAG, R=F.R_DIAG):

@@ -6,10 +6,30 @@ import re
 
 import pytest
 
-from helpers import _declared, _prototypes
+from helpers import INCLUDE, _declared, _prototypes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mpcqp.h")
+HEADER = os.path.join(INCLUDE, "mpcqp.h")
+# what each header under include/ declares: a count for mpcqp.h, whose names are the table's;
+# the names themselves for a companion, which adds to the ABI and keeps its version
+HEADERS = {
+    "mpcqp.h": 28,
+    "mpcqp_predict_abi.h": {"mpcqp_predict"},
+    "mpcqp_plant_abi.h": {"mpcqp_plant", "mpcqp_plant_reset", "mpcqp_set_plant"},
+    "mpcqp_certify_abi.h": {"mpcqp_certify"},
+    "mpcqp_gait_abi.h": {"mpcqp_set_gaits", "mpcqp_set_gait_schedule", "mpcqp_gait_schedule"},
+    "mpcqp_disturb_abi.h": {"mpcqp_sensors", "mpcqp_set_sensors", "mpcqp_push"},
+}
+ARGUMENTS = {"mpcqp_predict": 13, "mpcqp_certify": 13, "mpcqp_plant": 15, "mpcqp_plant_reset": 8,
+             "mpcqp_gait_schedule": 15, "mpcqp_sensors": 15, "mpcqp_set_sensors": 13, "mpcqp_push": 8}
+_ROLLOUT_ROW = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 10)
+ROWS = {"mpcqp_predict": _ROLLOUT_ROW, "mpcqp_certify": _ROLLOUT_ROW}
+# what a header's text says beside its declarations
+TEXT = {
+    "mpcqp_predict_abi.h": ("mpc.py:293-294",),
+    "mpcqp_certify_abi.h": ("first-order bound", "tight at the optimum and loose"),
+}
+# what the comment above each entry point of a header names: what the call replaces
+REPLACES = {"mpcqp_gait_abi.h": ("gait.py:", "scripts/mujoco_aliengo.py:121-155")}
 
 
 def test_header_and_binding_agree():
@@ -25,31 +45,66 @@ def _is_int32(t):
     return t in (ctypes.c_int32, ctypes.c_int) and ctypes.sizeof(t) == 4
 
 
-def test_binding_signatures_match_the_header():
-    """Every row of the binding table agrees with its declaration in include/mpcqp.h position by
-    position: a pointer is passed as a pointer, int32_t as a 32-bit int, double as c_double, and
-    the return type likewise.  A miscounted row would hand a kernel garbage pointers."""
+# mpcqp.h: a pointer is passed as a pointer (MpcqpParams* as POINTER(MpcqpParams)), int32_t as a 32-bit int
+MAIN_RULE = {"T*": _is_pointer, "int32_t": _is_int32, "int": _is_int32, "double": lambda t: t is ctypes.c_double}
+# a companion: the context, the stream and every array as c_void_p, each scalar as its own type
+COMPANION_RULE = {kind: (lambda t, want=want: t is want) for kind, want in
+                  {"T*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "double": ctypes.c_double,
+                   "uint64_t": ctypes.c_uint64}.items()}
+
+
+@pytest.mark.parametrize("header", list(HEADERS))
+def test_binding_table_matches_the_header(header):
+    """The header declares the functions of its part of the binding table, no other header declares
+    one of them, and every row agrees with its declaration position by position: a pointer is
+    passed as a pointer, int32_t as a 32-bit int, double as c_double, uint64_t as c_uint64, and
+    the return type likewise.  A miscounted row would hand a kernel garbage pointers.  load()
+    applied each row to an exported symbol, and the ABI version is the one a companion keeps."""
     from mpcqp import _lib
-    protos = _prototypes(HEADER)
-    assert set(protos) == _declared() == set(_lib.SIGNATURES) and len(protos) == 28
-    agrees = {"T*": _is_pointer, "int32_t": _is_int32, "int": _is_int32, "double": lambda t: t is ctypes.c_double}
+    main = header == "mpcqp.h"
+    assert list(_lib.ABI) == list(HEADERS)
+    assert sum(len(rows) for rows in _lib.ABI.values()) == len(_lib.SIGNATURES) == 39    # no name in two parts
+    protos, table = _prototypes(header), _lib.ABI[header]
+    assert set(protos) == set(table), (header, set(protos) ^ set(table))
+    if main:
+        assert len(protos) == HEADERS[header], (header, len(protos))
+    else:
+        assert set(protos) == HEADERS[header], (header, set(protos) ^ HEADERS[header])
+    for other in HEADERS:
+        twice = set(protos) & set(_prototypes(other)) if other != header else set()
+        assert not twice, (header, other, twice)
+    agrees = MAIN_RULE if main else COMPANION_RULE
+    lib = _lib.load()
     for name, (ret, kinds) in protos.items():
-        restype, argtypes = _lib.SIGNATURES[name]
+        restype, argtypes = table[name]
         assert len(argtypes) == len(kinds), (name, len(argtypes), len(kinds))
         for i, (kind, t) in enumerate(zip(kinds, argtypes)):
             assert kind in agrees, (name, i, kind)
             assert agrees[kind](t), (name, i, kind, t)
-        if ret == "void":
+        if not main:
+            assert ret == "int" and restype is ctypes.c_int, (name, ret, restype)
+        elif ret == "void":
             assert restype is None, name
         elif ret == "T*":
             assert restype is ctypes.c_char_p, name      # the one pointer returned: mpcqp_last_error's text
         else:
             assert ret in ("int", "int32_t") and _is_int32(restype), (name, ret, restype)
-    # the table is what load() applies
-    lib = _lib.load()
-    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        if name in ARGUMENTS:
+            assert len(kinds) == ARGUMENTS[name], (name, len(kinds))
+        if name in ROWS:
+            assert (restype, argtypes) == ROWS[name], name
+        # exported, and the table is what load() applies
+        assert _lib.SIGNATURES[name] is table[name], name
         fn = getattr(lib, name)
         assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert lib.mpcqp_abi_version() == _lib.ABI_VERSION == 6       # additive: the ABI version stays
+    src = open(os.path.join(INCLUDE, header)).read()
+    assert main or '#include "mpcqp.h"' in src, header
+    for text in TEXT.get(header, ()):
+        assert text in src, (header, text)
+    for name in protos if header in REPLACES else ():
+        comment = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int " + name + r"\(", src, re.S).group(1)
+        assert all(text in comment for text in REPLACES[header]), name
 
 
 def test_library_exports_every_declared_symbol():

@@ -21,18 +21,16 @@ Measured here (printed by the tests):
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import att_edge_checks
 import att_ref
-from helpers import _declared
+from helpers import _declared, host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 NEW_SYMBOLS = {"mpcqp_attitude", "mpcqp_set_attitude"}
 KNOWN = 1e-12
 F32_FLOOR = 2.4e-7      # two float32 ulps norm-wise, the project's floor for a float32 store
@@ -212,13 +210,8 @@ def test_trajectory_covers_the_cases(oracle):
 # ---- the header on the host
 
 @pytest.fixture(scope="module")
-def robot(tmp_path_factory):
-    d = tmp_path_factory.mktemp("att")
-    src, so = d / "shim.cpp", d / "libatt.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    lib = ctypes.CDLL(str(so))
+def robot():
+    lib = host_build(SHIM, name="att")
     lib.trust.restype = ctypes.c_double
     lib.trust.argtypes = [ctypes.c_int] * 5 + [ctypes.c_double]
     lib.launch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -41,37 +41,18 @@ Each one's LDS is one CertifyShared<NM, FULL> per workgroup, the size its static
 (csrc/mpcqp_certify.h)."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+from helpers import kernel_usage
 from mpcqp import build as B
 
 DENSE = ("mpcqp_kernel_64", "mpcqp_kernel_96", "mpcqp_kernel_128")
 
 
 @pytest.fixture(scope="module")
-def usage(tmp_path_factory):
-    """{mangled kernel name: {remark: value}} of one device-only compile."""
-    if not os.path.exists(B.HIPCC) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not installed")
-    cmd = [B.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-c",
-           "-I" + os.path.join(B.ROOT, "include"), "-o", str(tmp_path_factory.mktemp("build") / "dev.o"), B.SRC,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    usage = {}
-    name = None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and name:
-            usage[name][m.group(1).strip()] = int(m.group(2))
-    return usage
+def usage():
+    return kernel_usage()
 
 
 def test_dense_classes_are_spill_free(usage):

@@ -25,20 +25,18 @@ Measured here (printed by the tests):
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import certify_ref as cr
 import predict_ref as pr
-from helpers import _declared, _int_prototypes, oracle_solution
+from helpers import host_build, oracle_solution
 from oracle import formulation as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 CERTIFY_HEADER = os.path.join(ROOT, "include", "mpcqp_certify_abi.h")
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 KNOWN = 1e-12
 FD_BOUND = 64 * 2.0 ** -52
 SENTINEL = -77
@@ -70,30 +68,6 @@ extern "C" int max_horizon(void) { return PRD_MAX_N; }
 
 
 # ---- the ABI and Python surface
-
-def test_header_declares_certify_and_binding_agrees():
-    """mpcqp_certify is declared in the companion header include/mpcqp_certify_abi.h alone (mpcqp.h
-    and its binding table keep their functions, which tests/test_abi.py pins), and its binding
-    row agrees with the declaration position by position."""
-    from mpcqp import _lib
-    protos = _int_prototypes(CERTIFY_HEADER)
-    assert set(protos) == {"mpcqp_certify"} == set(_lib.CERTIFY_SIGNATURES)
-    assert _declared() == set(_lib.EXPORTED_SYMBOLS) and "mpcqp_certify" not in _declared()
-    restype, argtypes = _lib.CERTIFY_SIGNATURES["mpcqp_certify"]
-    assert (restype, argtypes) == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
-                                   + [ctypes.c_void_p] * 10)
-    kinds = protos["mpcqp_certify"]
-    assert len(kinds) == len(argtypes) == 13
-    for kind, t in zip(kinds, argtypes):
-        assert (kind == "T*" and t is ctypes.c_void_p) or (kind == "int32_t" and t is ctypes.c_int32), (kind, t)
-    lib = _lib.load()
-    fn = lib.mpcqp_certify                  # exported, and load() applied the row
-    assert fn.restype is restype and list(fn.argtypes) == argtypes
-    assert lib.mpcqp_abi_version() == 6     # additive: the ABI version stays
-    src = open(CERTIFY_HEADER).read()
-    assert '#include "mpcqp.h"' in src
-    assert "first-order bound" in src and "tight at the optimum and loose" in src
-
 
 def test_constants_match_binding(robot):
     from mpcqp import _lib
@@ -230,13 +204,8 @@ def test_finite_difference_identity(oracle_robots, N):
 # ---- the host-compiled header
 
 @pytest.fixture(scope="module")
-def robot(tmp_path_factory):
-    d = tmp_path_factory.mktemp("certify")
-    src, so = d / "shim.cpp", d / "libcertify.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    lib = ctypes.CDLL(str(so))
+def robot():
+    lib = host_build(SHIM, name="certify")
     vp = ctypes.c_void_p
     lib.launch.argtypes = [ctypes.c_int, ctypes.c_double, vp, vp, vp, ctypes.c_int] + [vp] * 10
     lib.launch.restype = None

@@ -15,21 +15,18 @@ Measured here (printed by the tests):
   mpcqp_sensors_kernel: ScratchSize 0, no vector or scalar register spilled, LDS 0, 58 VGPRs
   mpcqp_push_kernel:    ScratchSize 0, no register spilled, LDS 0
 """
-import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import disturb_ref as dr
 import plant_ref as pr
+from helpers import _vp, host_build, kernel_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp_disturb_abi.h")
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 # The worst difference of a bias word between the g++-compiled header and the restatement,
 # measured here: 0.  Both evaluate log, sin and cos by the same IEEE operations in the same order
 # (sense_log, sense_sincos_turn), and sqrt, / and rint are correctly rounded on both sides.
@@ -64,17 +61,8 @@ extern "C" int words(void) { return SENSE_WORDS; }
 
 
 @pytest.fixture(scope="module")
-def header(tmp_path_factory):
-    d = tmp_path_factory.mktemp("disturb")
-    src, so = d / "shim.cpp", d / "libdisturb.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    return ctypes.CDLL(str(so))
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+def header():
+    return host_build(SHIM, ("-O2", "-std=c++17", "-ffp-contract=off"), "disturb")
 
 
 def run_header(header, state, P, gyro=None, accel=None, dofs=None, touch=None, scale=None):
@@ -104,26 +92,6 @@ def plant_like(rng, B):
 
 
 # ---- the ABI and Python surface
-
-def test_header_declares_the_stage_and_binding_agrees():
-    from helpers import _declared, _int_prototypes
-    from mpcqp import _lib
-    protos = _int_prototypes(HEADER)
-    assert set(protos) == {"mpcqp_sensors", "mpcqp_set_sensors", "mpcqp_push"} == set(_lib.DISTURB_SIGNATURES)
-    assert _declared() == set(_lib.EXPORTED_SYMBOLS) and not set(protos) & _declared()
-    ctype = {"T*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "double": ctypes.c_double, "uint64_t": ctypes.c_uint64}
-    lib = _lib.load()
-    for name, kinds in protos.items():
-        restype, argtypes = _lib.DISTURB_SIGNATURES[name]
-        assert restype is ctypes.c_int and len(kinds) == len(argtypes), name
-        for i, (kind, t) in enumerate(zip(kinds, argtypes)):
-            assert ctype[kind] is t, (name, i, kind, t)
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes
-    assert len(protos["mpcqp_sensors"]) == 15 and len(protos["mpcqp_push"]) == 8 and len(protos["mpcqp_set_sensors"]) == 13
-    assert lib.mpcqp_abi_version() == 6           # additive: the ABI version stays
-    assert '#include "mpcqp.h"' in open(HEADER).read()
-
 
 def test_constants_agree(header):
     from mpcqp import _lib
@@ -508,26 +476,8 @@ def test_sensed_closed_loop_against_its_recorded_figures():
 # ---- the kernels' resources
 
 @pytest.fixture(scope="module")
-def usage(tmp_path_factory):
-    """{mangled kernel name: {remark: value}} of one device-only compile (as tests/test_build.py's)."""
-    from mpcqp import build as B
-    if not os.path.exists(B.HIPCC) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not installed")
-    cmd = [B.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-c",
-           "-I" + os.path.join(B.ROOT, "include"), "-o", str(tmp_path_factory.mktemp("build") / "dev.o"), B.SRC,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    usage, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and name:
-            usage[name][m.group(1).strip()] = int(m.group(2))
-    return usage
+def usage():
+    return kernel_usage()
 
 
 @pytest.mark.parametrize("kernel", ("mpcqp_sensors_kernel", "mpcqp_push_kernel"))

@@ -26,20 +26,18 @@ outputs 5.5e-08."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import est_ref
 import kin_ref
-from helpers import _declared
+from helpers import _declared, host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 NEW_SYMBOLS = {"mpcqp_estimate", "mpcqp_set_estimator"}
 KNOWN = 1e-5      # metres (and m/s): the known answers' bound
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 
 KERNEL_SHIM = r'''
 #include <barrier>
@@ -235,13 +233,8 @@ def test_nan_leaves_that_robot_alone():
 
 
 @pytest.fixture(scope="module")
-def kernel(tmp_path_factory):
-    d = tmp_path_factory.mktemp("est")
-    src, so = d / "shim.cpp", d / "libest.so"
-    src.write_text(KERNEL_SHIM)
-    subprocess.run(["g++", "-std=c++20", "-O2", "-ffp-contract=off", "-pthread", "-shared", "-fPIC", "-I", CSRC, "-o",
-                    str(so), str(src)], check=True)
-    return ctypes.CDLL(str(so))
+def kernel():
+    return host_build(KERNEL_SHIM, ("-std=c++20", "-O2", "-ffp-contract=off", "-pthread"), "est")
 
 
 def host_launch(kernel, state, inp, layout="split", constants=None, pad=2):

@@ -19,18 +19,16 @@ Measured here (printed by the tests):
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import gait_ref as gr
 import swing_ref
+from helpers import _vp, host_build, kernel_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAIT_HEADER = os.path.join(ROOT, "include", "mpcqp_gait_abi.h")
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 GAIT_LDS = 0           # only a lane that switches reads the library, nothing is staged
 IBMS = (1, 3, 20)
 
@@ -62,17 +60,8 @@ extern "C" int lib_max(void) { return GAIT_LIB_MAX; }
 
 
 @pytest.fixture(scope="module")
-def header(tmp_path_factory):
-    d = tmp_path_factory.mktemp("gait")
-    src, so = d / "shim.cpp", d / "libgait.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    return ctypes.CDLL(str(so))
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+def header():
+    return host_build(SHIM, ("-O2", "-std=c++17", "-ffp-contract=off"), "gait")
 
 
 def all_gaits():
@@ -109,34 +98,6 @@ def run_header(header, lib, c, flags, ibm, want, state, gait, tick, swing_mem=No
 
 
 # ---- the ABI and Python surface
-
-def test_header_declares_the_scheduler_and_binding_agrees():
-    """mpcqp_set_gaits, mpcqp_set_gait_schedule and mpcqp_gait_schedule are declared in the companion
-    header (mpcqp.h and its binding table keep their functions, which tests/test_abi.py pins), and
-    each binding row agrees with its declaration position by position."""
-    from helpers import _declared, _int_prototypes
-    from mpcqp import _lib
-    protos = _int_prototypes(GAIT_HEADER)
-    assert set(protos) == {"mpcqp_set_gaits", "mpcqp_set_gait_schedule", "mpcqp_gait_schedule"} == set(_lib.GAIT_SIGNATURES)
-    assert _declared() == set(_lib.EXPORTED_SYMBOLS) and not set(protos) & _declared()
-    ctype = {"T*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "double": ctypes.c_double}
-    lib = _lib.load()
-    for name, kinds in protos.items():
-        restype, argtypes = _lib.GAIT_SIGNATURES[name]
-        assert restype is ctypes.c_int and len(kinds) == len(argtypes), name
-        for i, (kind, t) in enumerate(zip(kinds, argtypes)):
-            assert ctype[kind] is t, (name, i, kind, t)
-        fn = getattr(lib, name)                   # exported, and load() applied the row
-        assert fn.restype is restype and list(fn.argtypes) == argtypes
-    assert len(protos["mpcqp_gait_schedule"]) == 15
-    assert lib.mpcqp_abi_version() == 6           # additive: the ABI version stays
-    src = open(GAIT_HEADER).read()
-    assert '#include "mpcqp.h"' in src
-    # each entry point says what it replaces
-    for name in protos:
-        comment = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int " + name + r"\(", src, re.S).group(1)
-        assert "gait.py:" in comment and "scripts/mujoco_aliengo.py:121-155" in comment, name
-
 
 def test_constants_agree(header):
     from mpcqp import _lib
@@ -554,26 +515,8 @@ def test_the_scheduled_closed_loop_switches_where_recorded_and_stays_up(loop):
 # ---- the kernel's resources
 
 @pytest.fixture(scope="module")
-def usage(tmp_path_factory):
-    """{mangled kernel name: {remark: value}} of one device-only compile (as tests/test_build.py's)."""
-    from mpcqp import build as B
-    if not os.path.exists(B.HIPCC) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not installed")
-    cmd = [B.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-c",
-           "-I" + os.path.join(B.ROOT, "include"), "-o", str(tmp_path_factory.mktemp("build") / "dev.o"), B.SRC,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    usage, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and name:
-            usage[name][m.group(1).strip()] = int(m.group(2))
-    return usage
+def usage():
+    return kernel_usage()
 
 
 def test_gait_kernel_has_no_private_memory_no_spills_and_no_lds(usage):

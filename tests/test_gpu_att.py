@@ -30,24 +30,19 @@ torch = pytest.importorskip("torch")
 import att_ref  # noqa: E402
 import est_ref  # noqa: E402
 import kin_ref  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 Q_BOUND = 10 * att_ref.D_Q
 F32_BOUND = 2.4e-7
 KNOWN = 1e-12
-DEV = "cuda:0"
 SENTINEL = -77.0
 W = 64                     # kAttThreads: robots per workgroup (csrc/mpcqp_attitude.h)
 TICKS, BMAX = 40, 2 * W + 3
 OUTS = ("quat", "gyro_out", "trust", "status")
 ALL = ("tick", "gait", "ibm", "touch")
 BIAS_ON = dict(kappa_ref=2.0, bias_gain=0.5)
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def new_engine():

@@ -33,19 +33,14 @@ torch = pytest.importorskip("torch")
 
 import certify_ref as cr  # noqa: E402
 import predict_ref as pr  # noqa: E402
-from helpers import oracle_solution  # noqa: E402
+from helpers import DEV, _dev, oracle_solution  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 CANARY = -77.0
 PAD = 2
 INPUTS = ("x0", "xref", "contact", "feet", "robot")
 OUTPUTS = ("G", "report", "status")
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(DEV).contiguous()
 
 
 def engine(N, Q=cr.Q_DIAG, R=cr.R_DIAG):

@@ -28,10 +28,10 @@ torch = pytest.importorskip("torch")
 import disturb_ref as dr  # noqa: E402
 import kin_ref  # noqa: E402
 import plant_ref as pr  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 N = 10
 T = 200
 SIZES = (1, 3, 4, 5, 63, 64, 65, 130)
@@ -45,11 +45,6 @@ CONFIGS = (dict(dr.MEMS, sigma_q=1e-3, touch_lag=2, p_drop=0.25),
 
 
 P_LSB = np.float32(CONFIGS[0]["q_lsb"] * 1.0001)
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def _bits(t):

@@ -26,22 +26,17 @@ torch = pytest.importorskip("torch")
 import est_ref  # noqa: E402
 import kin_ref  # noqa: E402
 from est_ref import norm_err  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 X_BOUND, P_BOUND = 10 * est_ref.D_X, 10 * est_ref.D_P
 F32_BOUND = max(2.4e-7, 10 * est_ref.D_X)
 KNOWN = 1e-5
-DEV = "cuda:0"
 SENTINEL = -77.0
 G = 3                      # kEstRobots: robots per workgroup (csrc/mpcqp_estimator.h)
 TICKS, BMAX = 40, 2 * G + 1
 OUTS = ("root_states", "feet_world", "status")
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 @pytest.fixture(scope="module")

@@ -22,18 +22,13 @@ torch = pytest.importorskip("torch")
 import gait_ref as gr  # noqa: E402
 import plant_ref as pr  # noqa: E402
 import swing_ref  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SENTINEL = -77
 N = 10
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gait_switch.npz")
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def _bits(t):

@@ -32,18 +32,13 @@ torch = pytest.importorskip("torch")
 
 import kin_ref  # noqa: E402
 from kin_ref import OUTPUTS, norm_err  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 BOUND = 2.4e-7
-DEV = "cuda:0"
 SENTINEL = -77.0
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 @pytest.fixture(scope="module")

@@ -29,6 +29,7 @@ def _engine(N, **kw):
 
 
 def _dev(a, dtype=None):
+    # not helpers._dev: this one converts on the host, before the copy to the device
     import torch
     t = torch.as_tensor(np.ascontiguousarray(a))
     if dtype is not None:

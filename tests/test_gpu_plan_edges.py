@@ -39,11 +39,11 @@ torch = pytest.importorskip("torch")
 
 from oracle.planner import GAITS, PlannerOracle, gait_table, quat2matrix, quat2zyx, world_velocity  # noqa: E402
 from oracle.planner import stance_torques as oracle_stance_torques  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-DEV = "cuda:0"
 SENTINEL = -77.0
 PAD = 3
 X0_RTOL, XREF_ATOL, STATE_ATOL = 2.4e-7, 2e-6, 1e-7
@@ -52,11 +52,6 @@ BMAX = 2 * W + 3
 T_PARITY, IBM = 41, 20
 X, Y, YAW, ROLL, PITCH, STARTED = range(6)     # the planner record (include/mpcqp.h)
 f32, f64 = np.float32, np.float64
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def new_engine(N=10):

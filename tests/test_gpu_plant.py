@@ -36,10 +36,10 @@ torch = pytest.importorskip("torch")
 
 import kin_ref  # noqa: E402
 import plant_ref as pr  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SENTINEL = -77.0
 N = 10
 # ten times the worst single-tick error of the first green run on the MI355X (1.04e-16 at B = 1,
@@ -47,11 +47,6 @@ N = 10
 DEVICE_BOUND = 7.3e-15
 F32_BOUND = 2.0 ** -23
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plant_tau.npz")
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def _bits(t):

@@ -31,20 +31,15 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import predict_ref as pr  # noqa: E402
-from helpers import oracle_solution  # noqa: E402
+from helpers import DEV, _dev, oracle_solution  # noqa: E402
 from oracle import formulation as F  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 CANARY = -77.0
 PAD = 2
 J_BOUND = 10 * pr.D_J
 INPUTS = ("x0", "xref", "contact", "feet", "robot")
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(DEV).contiguous()
 
 
 def engine(N, Q=pr.Q_DIAG, R=pr.R_DIAG):

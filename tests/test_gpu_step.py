@@ -32,10 +32,10 @@ torch = pytest.importorskip("torch")
 
 import kin_ref  # noqa: E402
 import swing_ref  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SENTINEL = -77.0
 N, IBM, T = 10, 2, 44
 BATCHES = (1, 3, 64, 65, 130)    # alone, a partial workgroup, one exactly, one robot past it, three with a tail
@@ -45,11 +45,6 @@ SWING_OUT = ("swing_state", "pos_target", "vel_target")
 KIN_OUT = ("thighs", "pos_feet", "foot_pos_base", "foot_vel_base", "jac")
 MPC_OUT = ("xref", "contact", "feet")
 OPTIONAL = SWING_OUT + KIN_OUT
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def _bits(a):

@@ -25,16 +25,11 @@ torch = pytest.importorskip("torch")
 
 import swing_ref  # noqa: E402
 from swing_ref import norm_err, run_ref  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 BOUND = 4.61e-7
-DEV = "cuda:0"
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def _engine(kp=700.0, kd=20.0, **kw):

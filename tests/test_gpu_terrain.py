@@ -34,10 +34,10 @@ torch = pytest.importorskip("torch")
 
 import swing_ref  # noqa: E402
 import terrain_ref as tr  # noqa: E402
+from helpers import DEV, _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 W = 64
 BATCHES = (1, W - 1, W, W + 1, 2 * W + 3)
 N_BOUND = 10 * tr.D_N
@@ -45,11 +45,6 @@ F32_BOUND = 2.4e-7
 SWING_BOUND = 4.61e-7          # tests/test_gpu_swing.py BOUND
 CANARY = -77.0
 OUTPUTS = ("normal", "plane", "normal_base", "status")
-
-
-def _dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
-    return (t.to(dtype) if dtype is not None else t).contiguous()
 
 
 def _bits(a):

@@ -2,14 +2,11 @@
 compiled for the host with g++ -- the multiplier check that decides whether a
 polished active set is the optimum (g in the cone of the foot's active rows)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
+from helpers import host_build
 
 SHIM = r'''
 #include "mpcqp_ipm_foot.h"
@@ -45,12 +42,8 @@ extern "C" void inverse3(const double* a, double* o) {
 
 
 @pytest.fixture(scope="module")
-def foot(tmp_path_factory):
-    d = tmp_path_factory.mktemp("foot")
-    src, so = d / "shim.cpp", d / "libfoot.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)], check=True)
-    lib = ctypes.CDLL(str(so))
+def foot():
+    lib = host_build(SHIM, ("-O2",), "foot")
     dp = ctypes.POINTER(ctypes.c_double)
     lib.cone_mult.argtypes = [dp, ctypes.c_int, ctypes.c_int, dp, ctypes.c_double, dp, ctypes.POINTER(ctypes.c_int)]
     lib.inverse3.argtypes = [dp, dp]

@@ -10,17 +10,15 @@ error is what remains.  See CPU_BOUND below and the docstring of tests/test_gpu_
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import _declared
+from helpers import _declared, host_build
 import kin_edge_checks
 import kin_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 
 # Against kin.npz the restatements carry only float64 rounding (1e-15) and, in jac and
@@ -83,13 +81,8 @@ def fx():
 
 
 @pytest.fixture(scope="module")
-def leg(tmp_path_factory):
-    d = tmp_path_factory.mktemp("kin")
-    src, so = d / "shim.cpp", d / "libkin.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    lib = ctypes.CDLL(str(so))
+def leg():
+    lib = host_build(SHIM, name="kin")
     dp, fp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)
     lib.robot.argtypes = [dp] + [fp] * 7 + [dp] * 6
     lib.robot.restype = None

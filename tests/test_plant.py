@@ -26,18 +26,16 @@ Measured here (printed by the tests):
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import kin_ref
 import plant_ref as pr
+from helpers import _vp, host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 PLANT_HEADER = os.path.join(ROOT, "include", "mpcqp_plant_abi.h")
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 CPU_BOUND = 1e-12      # both sides are float64 with libm: the gap is rounding
 IK_BOUND = 1e-13
 
@@ -70,18 +68,10 @@ extern "C" double ik_eps(void) { return PLANT_IK_EPS; }
 
 
 @pytest.fixture(scope="module")
-def header(tmp_path_factory):
-    d = tmp_path_factory.mktemp("plant")
-    src, so = d / "shim.cpp", d / "libplant.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)], check=True)
-    lib = ctypes.CDLL(str(so))
+def header():
+    lib = host_build(SHIM, name="plant")
     lib.ik_eps.restype = ctypes.c_double
     return lib
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _par(par):
@@ -104,29 +94,6 @@ def run_header(lib, rec, tau, robot, geom, par, plane=None):
 
 
 # ---- the ABI and Python surface
-
-def test_header_declares_the_plant_and_binding_agrees():
-    """mpcqp_plant, mpcqp_plant_reset and mpcqp_set_plant are declared in the companion header
-    (mpcqp.h and its binding table keep their functions, which tests/test_abi.py pins), and each
-    binding row agrees with its declaration position by position."""
-    from helpers import _declared, _int_prototypes
-    from mpcqp import _lib
-    protos = _int_prototypes(PLANT_HEADER)
-    assert set(protos) == {"mpcqp_plant", "mpcqp_plant_reset", "mpcqp_set_plant"} == set(_lib.PLANT_SIGNATURES)
-    assert _declared() == set(_lib.EXPORTED_SYMBOLS) and not set(protos) & _declared()
-    ctype = {"T*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "double": ctypes.c_double}
-    lib = _lib.load()
-    for name, kinds in protos.items():
-        restype, argtypes = _lib.PLANT_SIGNATURES[name]
-        assert restype is ctypes.c_int and len(kinds) == len(argtypes), name
-        for i, (kind, t) in enumerate(zip(kinds, argtypes)):
-            assert ctype[kind] is t, (name, i, kind, t)
-        fn = getattr(lib, name)                   # exported, and load() applied the row
-        assert fn.restype is restype and list(fn.argtypes) == argtypes
-    assert len(protos["mpcqp_plant"]) == 15 and len(protos["mpcqp_plant_reset"]) == 8
-    assert lib.mpcqp_abi_version() == 6           # additive: the ABI version stays
-    assert '#include "mpcqp.h"' in open(PLANT_HEADER).read()
-
 
 def test_strides_agree(header):
     from mpcqp import _lib, params

@@ -22,19 +22,17 @@ Measured here (printed by the tests):
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import predict_ref as pr
-from helpers import _declared, _int_prototypes, oracle_solution
+from helpers import host_build, oracle_solution
 from oracle import formulation as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 PREDICT_HEADER = os.path.join(ROOT, "include", "mpcqp_predict_abi.h")
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "predict.npz")
 KNOWN = 1e-12
 SENTINEL = -77
@@ -57,29 +55,6 @@ extern "C" int max_horizon(void) { return PRD_MAX_N; }
 
 
 # ---- the ABI and Python surface
-
-def test_header_declares_predict_and_binding_agrees():
-    """mpcqp_predict is declared in the companion header include/mpcqp_predict_abi.h (mpcqp.h and
-    its binding table keep their 28 functions, which tests/test_abi.py pins), and its binding row
-    agrees with the declaration position by position."""
-    from mpcqp import _lib
-    protos = _int_prototypes(PREDICT_HEADER)
-    assert set(protos) == {"mpcqp_predict"} == set(_lib.PREDICT_SIGNATURES)
-    assert _declared() == set(_lib.EXPORTED_SYMBOLS) and "mpcqp_predict" not in _declared()
-    restype, argtypes = _lib.PREDICT_SIGNATURES["mpcqp_predict"]
-    assert (restype, argtypes) == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
-                                   + [ctypes.c_void_p] * 10)
-    kinds = protos["mpcqp_predict"]
-    assert len(kinds) == len(argtypes) == 13
-    for kind, t in zip(kinds, argtypes):
-        assert (kind == "T*" and t is ctypes.c_void_p) or (kind == "int32_t" and t is ctypes.c_int32), (kind, t)
-    lib = _lib.load()
-    fn = lib.mpcqp_predict                  # exported, and load() applied the row
-    assert fn.restype is restype and list(fn.argtypes) == argtypes
-    assert lib.mpcqp_abi_version() == 6     # additive: the ABI version stays
-    src = open(PREDICT_HEADER).read()
-    assert "mpc.py:293-294" in src and '#include "mpcqp.h"' in src
-
 
 def test_constants_match_binding(robot):
     from mpcqp import _lib
@@ -178,13 +153,8 @@ def test_restatement_matches_the_oracle_sx_su(N):
 # ---- the host-compiled header
 
 @pytest.fixture(scope="module")
-def robot(tmp_path_factory):
-    d = tmp_path_factory.mktemp("predict")
-    src, so = d / "shim.cpp", d / "libpredict.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    lib = ctypes.CDLL(str(so))
+def robot():
+    lib = host_build(SHIM, name="predict")
     vp = ctypes.c_void_p
     lib.launch.argtypes = [ctypes.c_int, ctypes.c_double, vp, vp, vp, ctypes.c_int] + [vp] * 10
     lib.launch.restype = None

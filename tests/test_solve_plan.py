@@ -4,14 +4,11 @@ the launches' schedule (order, priority, interior-point layout, fork).  The sche
 changes a result, so no parity test on the GPU can see it: it is checked here, against plans
 written out by hand from the rules and against the rules' invariants over a grid."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
+from helpers import host_build
 
 # one row of ints per plan, in this order
 FIELDS = ("first", "l64", "l96", "l128", "lipm", "queues", "order", "order_mode", "order_segs", "prio",
@@ -41,12 +38,8 @@ DENSE_N, MAX_N = 20, 32
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("solve_plan")
-    src, so = d / "shim.cpp", d / "libplan.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)], check=True)
-    so_lib = ctypes.CDLL(str(so))
+def lib():
+    so_lib = host_build(SHIM, ("-std=c++17", "-O2"), "plan")
     ip = ctypes.POINTER(ctypes.c_int)
     so_lib.plans.argtypes = [ctypes.c_int, ip, ip]
     so_lib.constants.argtypes = [ip]

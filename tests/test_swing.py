@@ -11,17 +11,15 @@ fixture tests): see CPU_BOUND below and the docstring of tests/test_gpu_swing.py
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from helpers import _declared
+from helpers import _declared, host_build
 import swing_ref
 from swing_ref import SwingRef, quat2matrix_f32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
 
 # The restatements differ from the recorded run by the reference's float32
@@ -104,13 +102,8 @@ def fxe():
 
 
 @pytest.fixture(scope="module")
-def leg(tmp_path_factory):
-    d = tmp_path_factory.mktemp("swing")
-    src, so = d / "shim.cpp", d / "libswing.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    lib = ctypes.CDLL(str(so))
+def leg():
+    lib = host_build(SHIM, name="swing")
     dp, fp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
     lib.decide.argtypes = [ctypes.c_int] * 5 + [dp]
     lib.curve.argtypes = [ctypes.c_double, ctypes.c_double, dp, dp, ctypes.c_double, dp, dp]

@@ -21,17 +21,15 @@ Measured here (printed by the tests):
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import terrain_ref as tr
-from helpers import _declared
+from helpers import _declared, host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mpcqp.h")
-CSRC = os.path.join(ROOT, "pympc-quadruped_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "terrain.npz")
 NEW_SYMBOLS = {"mpcqp_terrain", "mpcqp_set_terrain", "mpcqp_set_ground"}
 KNOWN = 1e-12
@@ -105,13 +103,8 @@ def test_python_surface():
 
 
 @pytest.fixture(scope="module")
-def robot(tmp_path_factory):
-    d = tmp_path_factory.mktemp("terrain")
-    src, so = d / "shim.cpp", d / "libterrain.so"
-    src.write_text(SHIM)
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)],
-                   check=True)
-    lib = ctypes.CDLL(str(so))
+def robot():
+    lib = host_build(SHIM, name="terrain")
     vp = ctypes.c_void_p
     lib.launch.argtypes = [vp, ctypes.c_int, ctypes.c_int] + [vp] * 9
     lib.launch.restype = None
