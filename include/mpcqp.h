@@ -574,7 +574,15 @@ int mpcqp_set_attitude(mpcqp_ctx* ctx, double dt, double gravity, double kappa_r
  *                  contact > contact_threshold (a NaN is no contact).
  *                  MPCQP_TERRAIN_ROOT_STATES: `quat` is an Isaac Gym root-state tensor [B][13];
  *                  without it [B][4] as (w, x, y, z)
- *   pos_feet       [B][4][3]  the feet in the world frame (mpcqp_kinematics' pos_feet,
+ *                  MPCQP_TERRAIN_GROUND: `plane` is written for mpcqp_set_ground.  The latched
+ *                  feet are foot centres, and the swing leg places a foothold at touchdown_z +
+ *                  ground(x, y): under this flag the fourth word of `plane` is
+ *                  d - n_z touchdown_z (float64 from the record, rounded once; touchdown_z as
+ *                  mpcqp_set_swing left it), so that a foothold lies on the fitted plane
+ *                  n . p = d itself -- on level ground at the height the feet were latched at,
+ *                  as with no ground registered.  The record, `normal`, `normal_base` and
+ *                  `robot` are the same with and without it.
+ *   pos_feet      [B][4][3]  the feet in the world frame (mpcqp_kinematics' pos_feet,
  *                             mpcqp_estimate's feet_world)
  *   contact        [B][4]
  *   quat           nullable; read for normal_base alone
@@ -586,6 +594,7 @@ int mpcqp_set_attitude(mpcqp_ctx* ctx, double dt, double gravity, double kappa_r
  * Outputs, each nullable (a NULL output is not written):
  *   normal         [B][3]  n, unit length, n_z > 0
  *   plane          [B][4]  n, d: the plane n . p = d through the centroid of the history
+ *                          (n, d - n_z touchdown_z under MPCQP_TERRAIN_GROUND)
  *   normal_base    [B][3]  R_base^T n (terrain_normal_est_yaw_aligned, :227), R_base the float32
  *                          quat2matrix of mpcqp_plan; needs quat
  *   status         [B]     MPCQP_STATUS_OK, or MPCQP_STATUS_NONFINITE for a robot with a
@@ -615,6 +624,7 @@ int mpcqp_set_attitude(mpcqp_ctx* ctx, double dt, double gravity, double kappa_r
 #define MPCQP_TERRAIN_STRIDE 20      /* doubles per robot */
 #define MPCQP_TERRAIN_SWING_STATE 1
 #define MPCQP_TERRAIN_ROOT_STATES 2
+#define MPCQP_TERRAIN_GROUND 4
 int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos_feet, const float* contact,
                   const float* quat, double* terrain_state, float* robot, float* normal, float* plane,
                   float* normal_base, int32_t* status, void* stream);
@@ -632,7 +642,10 @@ int mpcqp_set_terrain(mpcqp_ctx* ctx, double contact_threshold, double flat_tol,
  * z = touchdown_z + ground(x, y), ground(x, y) = (d - n_x x - n_y y) / n_z, and its swing apex
  * at swing_height + (ground(lift-off) + ground(foothold)) / 2.  A plane that is non-finite or
  * has n_z <= 0 counts as none, as does b >= capacity: that robot walks on the reference's flat
- * ground, bitwise as with nothing registered.  Stance legs do not read it.  NULL or capacity 0
+ * ground, bitwise as with nothing registered.  Stance legs do not read it.  ground(x, y) is
+ * the height of the surface under a foot whose centre rides -touchdown_z above it; a plane
+ * fitted through foot centres (mpcqp_terrain) is handed over with MPCQP_TERRAIN_GROUND, which
+ * subtracts n_z touchdown_z from d so that the foothold lies on the fitted plane.  NULL or capacity 0
  * disables; capacity < 0, or a NULL plane with capacity > 0, returns MPCQP_ERR_ARG. */
 int mpcqp_set_ground(mpcqp_ctx* ctx, const float* plane, int32_t capacity);
 

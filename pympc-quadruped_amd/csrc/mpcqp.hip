@@ -74,6 +74,7 @@ static_assert(TER_STRIDE == MPCQP_TERRAIN_STRIDE, "terrain record stride");
 static_assert(TER_ROBOT_STRIDE == MPCQP_ROBOT_STRIDE && TER_ROBOT_NORMAL == MPCQP_ROBOT_NORMAL &&
                   MPCQP_ROBOT_NORMAL + 3 <= MPCQP_ROBOT_STRIDE, "the normal's words of the robot record");
 static_assert(TER_SWING_STATE == MPCQP_TERRAIN_SWING_STATE && TER_ROOT_STATES == MPCQP_TERRAIN_ROOT_STATES, "flags");
+static_assert(TER_GROUND == MPCQP_TERRAIN_GROUND, "flags");
 static_assert(TER_STATUS_OK == MPCQP_STATUS_OK && TER_STATUS_NONFINITE == MPCQP_STATUS_NONFINITE, "status words");
 static_assert(SCHED_STRIDE == MPCQP_SCHED_STRIDE && GAIT_WORDS == MPCQP_GAIT_STRIDE && GAIT_LIB_MAX == MPCQP_GAIT_MAX &&
                   GAIT_SWING_WORDS == MPCQP_SWING_STRIDE && GAIT_ADVANCE == MPCQP_GAIT_ADVANCE, "scheduler record and library");
@@ -158,7 +159,7 @@ struct mpcqp_ctx {
   AttParams att{0.001, 9.81, 0.1, 0.0, 0.2, 0.0};
   // terrain-plane constants (mpcqp_set_terrain): a contact flag of 1 counts, the fit unfiltered as
   // in the reference, held where the feet are nearly collinear or the plane steeper than 60 degrees
-  TerParams ter{0.5, 1e-3, 0.5, 1.0, 0};
+  TerParams ter{0.5, 1e-3, 0.5, 1.0, 0, 0.0};
   const float* ground = nullptr;   // the swing leg's ground planes (caller-owned device buffer), mpcqp_set_ground
   int ground_cap = 0;
   // plant constants (mpcqp_set_plant); ground_z follows the swing's touchdown_z until it is set
@@ -947,7 +948,7 @@ int mpcqp_set_terrain(mpcqp_ctx* ctx, double contact_threshold, double flat_tol,
   if (!(cos_max_tilt > 0.0) || cos_max_tilt > 1.0)
     return set_err(ctx, MPCQP_ERR_ARG, "terrain: cos_max_tilt outside (0, 1]");
   if (!(blend > 0.0) || blend > 1.0) return set_err(ctx, MPCQP_ERR_ARG, "terrain: blend outside (0, 1]");
-  ctx->ter = TerParams{contact_threshold, flat_tol, cos_max_tilt, blend, 0};
+  ctx->ter = TerParams{contact_threshold, flat_tol, cos_max_tilt, blend, 0, 0.0};
   return MPCQP_OK;
 }
 
@@ -964,7 +965,7 @@ int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos
                   const float* quat, double* terrain_state, float* robot, float* normal, float* plane,
                   float* normal_base, int32_t* status, void* stream) {
   if (!ctx) return MPCQP_ERR_ARG;
-  if (flags & ~(MPCQP_TERRAIN_SWING_STATE | MPCQP_TERRAIN_ROOT_STATES))
+  if (flags & ~(MPCQP_TERRAIN_SWING_STATE | MPCQP_TERRAIN_ROOT_STATES | MPCQP_TERRAIN_GROUND))
     return set_err(ctx, MPCQP_ERR_ARG, "unknown terrain flags");
   if (batch < 0) return set_err(ctx, MPCQP_ERR_ARG, "terrain: batch < 0");
   if (!pos_feet || !contact || !terrain_state)
@@ -976,6 +977,7 @@ int mpcqp_terrain(mpcqp_ctx* ctx, int32_t batch, int32_t flags, const float* pos
   if (!dev.ok) return set_err(ctx, MPCQP_ERR_HIP, "hipSetDevice failed");
   TerParams tp = ctx->ter;
   tp.flags = flags;
+  tp.touchdown_z = ctx->touchdown_z;   // as mpcqp_set_swing left it: the swing leg of the next launch reads the same
   hipLaunchKernelGGL(mpcqp_terrain_kernel, dim3((batch + kTerThreads - 1) / kTerThreads), dim3(kTerThreads), 0,
                      (hipStream_t)stream, tp, (int)batch, pos_feet, contact, quat, terrain_state, robot, normal, plane,
                      normal_base, status);

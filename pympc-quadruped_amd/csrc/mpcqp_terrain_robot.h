@@ -23,12 +23,16 @@
 constexpr int TER_HIST = 0, TER_INIT = 12, TER_N = 13, TER_D = 16, TER_FITTED = 17, TER_STRIDE = 20;
 constexpr int TER_STATUS_OK = 0, TER_STATUS_NONFINITE = 4;   // MPCQP_STATUS_OK, MPCQP_STATUS_NONFINITE
 constexpr int TER_SWING_STATE = 1, TER_ROOT_STATES = 2;      // MPCQP_TERRAIN_SWING_STATE, MPCQP_TERRAIN_ROOT_STATES
+constexpr int TER_GROUND = 4;   // MPCQP_TERRAIN_GROUND: `plane` is the swing leg's ground, d - n_z touchdown_z
 constexpr int TER_ROBOT_STRIDE = 16, TER_ROBOT_NORMAL = 9;   // MPCQP_ROBOT_STRIDE, MPCQP_ROBOT_NORMAL: the cone rows' normal
 constexpr int TER_SWEEPS = 6;   // 4 reach numpy.linalg.eigh's vector to 3e-15, 3 leave 2e-5
 
 struct TerParams {
   double contact_threshold, flat_tol, cos_max_tilt, blend;
   int flags;
+  // the swing leg's (mpcqp_set_swing); read under TER_GROUND alone.  Last, so that an initialiser
+  // list that stops at `flags` keeps its meaning and leaves this zero
+  double touchdown_z;
 };
 
 // a tenth of a record: the record is 16-byte aligned, so it moves as ten of these
@@ -207,7 +211,10 @@ __host__ __device__ inline bool ter_contact(const TerParams& tp, float value) {
 
 // Robot b's share of mpcqp_terrain: `quat`, `robot` and every output are nullable.  A refused
 // robot: the record is not written, the status is TER_STATUS_NONFINITE and the outputs come
-// from the record as it was.
+// from the record as it was.  The latched feet are foot centres, and the swing leg places a
+// foothold at touchdown_z + ground(x, y) (mpcqp_set_ground): under TER_GROUND the fourth word of
+// `plane` is d - n_z touchdown_z, the plane whose ground() + touchdown_z is the fitted plane
+// itself, so that a foothold lands on n . p = d.  The record keeps d.
 __host__ __device__ inline void ter_robot(const TerParams& tp, size_t b, const float* pos_feet, const float* contact,
                                           const float* quat, double* terrain_state, float* robot, float* normal,
                                           float* plane, float* normal_base, int32_t* status) {
@@ -245,7 +252,8 @@ __host__ __device__ inline void ter_robot(const TerParams& tp, size_t b, const f
   if (plane != nullptr) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) plane[4 * b + k] = n32[k];
-    plane[4 * b + 3] = (float)out[TER_D];
+    plane[4 * b + 3] =
+        (tp.flags & TER_GROUND) ? (float)(out[TER_D] - out[TER_N + 2] * tp.touchdown_z) : (float)out[TER_D];
   }
   if (normal_base != nullptr) {   // R_base^T n (:227), R_base the float32 quat2matrix widened
     float qw, qx, qy, qz;

@@ -39,6 +39,7 @@ ATT_STRIDE = 8      # MPCQP_ATT_STRIDE: float64 orientation record per robot (q[
 TERRAIN_STRIDE = 20        # MPCQP_TERRAIN_STRIDE: float64 terrain record per robot (history[4][3], initialised, n[3], d, fitted)
 TERRAIN_SWING_STATE = 1    # MPCQP_TERRAIN_SWING_STATE: contact is a swing_state, stance where !(value > 0)
 TERRAIN_ROOT_STATES = 2    # MPCQP_TERRAIN_ROOT_STATES: quat is a root-state tensor [B,13]
+TERRAIN_GROUND = 4         # MPCQP_TERRAIN_GROUND: plane is the swing leg's ground, (n, d - n_z touchdown_z)
 PLANT_STRIDE = 48          # MPCQP_PLANT_STRIDE (mpcqp_plant_abi.h): float64 plant record per robot (pos, quat, vel, omega, feet, foot velocities, contact, flag word, call count)
 PLANT_MAX_SUBSTEPS = 16    # MPCQP_PLANT_MAX_SUBSTEPS (mpcqp_plant_abi.h)
 PREDICT_REPORT = 4         # MPCQP_PREDICT_REPORT (mpcqp_predict_abi.h): float64 report per robot (cost, cost_free, cone margin, swing residual)

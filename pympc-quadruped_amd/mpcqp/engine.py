@@ -722,7 +722,7 @@ class LinearMpc:
         self._ground = plane   # the context holds its pointer: keep it alive
 
     def terrain(self, terrain_state, pos_feet, contact=None, swing_state=None, quat=None, root_states=None,
-                robot=None, normal=None, plane=None, normal_base=None, status=None, stream=None):
+                robot=None, normal=None, plane=None, normal_base=None, status=None, stream=None, ground=False):
         """One tick of every robot's terrain plane (include/mpcqp.h mpcqp_terrain): the feet in the
         world frame and their contact state in, the ground plane fitted to the feet last in
         contact out, in one launch on the current stream.
@@ -733,7 +733,9 @@ class LinearMpc:
         place (in contact where not > 0); for normal_base, quat [B,4] (w, x, y, z) or
         ``root_states`` [B,13].  ``robot`` [B,16]: its words 9..11, the cone rows' surface
         normal, are overwritten.  Outputs, each optional: normal [B,3], plane [B,4] (n, d),
-        normal_base [B,3], status [B].  A tensor of another size, dtype or device, or one
+        normal_base [B,3], status [B].  ``ground`` (MPCQP_TERRAIN_GROUND): plane is written as
+        the swing leg's ground, (n, d - n_z touchdown_z), so that a foothold of ``set_ground``
+        lies on the fitted plane.  A tensor of another size, dtype or device, or one
         that is not contiguous, raises ValueError: the kernel reads and writes B rows of each."""
         s = self._stream_ptr(stream)
         if (contact is None) == (swing_state is None):
@@ -759,7 +761,7 @@ class LinearMpc:
                     and t.numel() == int(np.prod(shape))):
                 raise ValueError(f"terrain: {name} must be a contiguous {dtype} tensor of shape {list(shape)} on "
                                  f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        flags = 0
+        flags = _lib.TERRAIN_GROUND if ground else 0
         if swing_state is not None:
             flags, contact = flags | _lib.TERRAIN_SWING_STATE, swing_state
         if root_states is not None:

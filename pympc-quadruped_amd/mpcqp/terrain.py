@@ -32,11 +32,19 @@ class BatchedTerrain:
       attach:     with a controller, write the normal into ``controller.robot`` (words 9..11,
                   read by the next solve's cone rows) and register ``plane`` as the swing
                   leg's ground (LinearMpc.set_ground)
+      ground:     what ``plane`` is.  "feet" (the default when attached): the latched points
+                  are foot centres, where the swing leg's footholds belong, and ``plane`` is
+                  (n, d - n_z touchdown_z), the ground under them by the swing leg's own
+                  touchdown_z -- a foothold then lies on the fitted plane, and level ground
+                  walks as with no terrain stage.  "surface" (the default otherwise): ``plane``
+                  is the fitted (n, d) itself, for a simulator whose foot centres ride
+                  -touchdown_z above the surface that the latched points lie on
       constants:  any of LinearMpc.set_terrain's (contact_threshold, flat_tol, cos_max_tilt,
                   blend); they are the engine's, so a shared engine has one set
     """
 
-    def __init__(self, batch, controller=None, engine=None, device="cuda:0", attach=True, **constants):
+    def __init__(self, batch, controller=None, engine=None, device="cuda:0", attach=True, ground=None,
+                 **constants):
         self.B = B = int(batch)
         if controller is not None and controller.B != B:
             raise ValueError(f"the controller has {controller.B} robots, the terrain {B}")
@@ -56,7 +64,13 @@ class BatchedTerrain:
         self._normal_base = torch.zeros((B, 3), **f32)
         self._status = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.robot = None
-        if controller is not None and attach:
+        attached = controller is not None and attach
+        if ground is None:
+            ground = "feet" if attached else "surface"
+        if ground not in ("feet", "surface"):
+            raise ValueError(f"ground must be 'feet' or 'surface', got {ground!r}")
+        self.ground = ground
+        if attached:
             self.robot = controller.robot
             self.engine.set_ground(self._plane)
 
@@ -95,12 +109,14 @@ class BatchedTerrain:
         elif root_states is not None:
             kw.update(root_states=self._f32(root_states, (B, 13)), normal_base=self._normal_base)
         self.engine.terrain(self.terrain_state, self._f32(pos_feet, (B, 4, 3)), robot=self.robot,
-                            normal=self._normal, plane=self._plane, status=self._status, **kw)
+                            normal=self._normal, plane=self._plane, status=self._status,
+                            ground=self.ground == "feet", **kw)
         return self._normal
 
     def reset(self, robots=None):
         """Zero the records of all or some robots: the next update seeds their history with
-        all four feet.  Their outputs return to the level plane through the origin."""
+        all four feet.  Their outputs return to (0, 0, 1, 0), on which the swing leg walks as
+        with no ground registered."""
         idx = slice(None) if robots is None else robots
         self.terrain_state[idx] = 0.0
         level = torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float32, device=self.device)
@@ -116,7 +132,8 @@ class BatchedTerrain:
 
     @property
     def plane(self):
-        """(n, d) [B,4] float32: the plane n . p = d through the centroid of the history."""
+        """(n, d) [B,4] float32: the plane n . p = d through the centroid of the history; with
+        ground="feet" its fourth word is d - n_z touchdown_z, the swing leg's ground."""
         return self._plane
 
     @property

@@ -312,14 +312,49 @@ def euler_zyx(quat):
     return np.arctan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y)), np.arcsin(np.clip(2 * (w * y - z * x), -1, 1))
 
 
+def tilt_pose(root, tilt, azimuth, par):
+    """A level pose turned rigidly about the origin onto a slope: root [B,13] float32 (stand_pose's),
+    tilt [B] rad, azimuth [B] rad, the compass direction in which the ground climbs (0: along +x,
+    uphill for a robot that walks forward; pi / 2: it climbs to the robot's left; pi: downhill).
+    Position, velocities and quaternion are turned by the rotation R that takes e_z to
+    n = (-sin tilt cos az, -sin tilt sin az, cos tilt); a point at height ground_z over the level
+    ground lies on n . p = ground_z afterwards.  Returns (root [B,13] float32, plane [B,4]
+    float32 = (R e_z, ground_z))."""
+    root = np.asarray(root, np.float32).astype(np.float64)
+    B = root.shape[0]
+    tilt, az = np.broadcast_to(np.asarray(tilt, np.float64), (B,)), np.broadcast_to(np.asarray(azimuth, np.float64), (B,))
+    axis = np.stack([np.sin(az), -np.cos(az), np.zeros(B)], -1)                      # z x n / |z x n|
+    qt = np.concatenate([np.cos(tilt / 2)[:, None], np.sin(tilt / 2)[:, None] * axis], -1)
+    Rt = _rot(qt)
+    out = root.copy()
+    for k in (0, 7, 10):
+        out[:, k:k + 3] = _mv(Rt, root[:, k:k + 3])
+    q = _quat_mul(qt, np.concatenate([root[:, 6:7], root[:, 3:6]], 1))
+    out[:, 3:6], out[:, 6] = q[:, 1:4], q[:, 0]
+    plane = np.concatenate([Rt[:, :, 2], np.full((B, 1), par.ground_z)], 1).astype(np.float32)
+    return out.astype(np.float32), plane
+
+
 def closed_loop(commands, ticks, robot="aliengo", gait="trot10", horizon=10, ibm=20, par=None, record_tau=False,
-                heights=None):
+                heights=None, plane=None, terrain=None, terrain_ground=True):
     """The control loop on the CPU oracles, one robot per entry of ``commands`` (forward speeds,
     m/s): plant outputs -> kin_ref -> oracle.planner -> oracle.cpu_port (MPC ticks) ->
     swing_ref.SwingRef -> plant_step.  Returns per-tick arrays: height, roll, pitch, x [T,B],
     solve_ok [T,B] bool, finite [T,B] bool, touch [T,B,4]; with record_tau also tau [T,B,12]
     float32 and the starting records.  ``heights``: each robot's starting base height (default:
-    the preset's desired height)."""
+    the preset's desired height).
+
+    ``plane`` [B,4]: the plant's ground, (n, ground_z) of tilt_pose, whose rotation the stand pose
+    is started under; None: level.  ``terrain``: a dict of terrain constants (may be empty) runs
+    the terrain stage in the order of ``ctl.step(...); ter.update()``: the tick's swing leg
+    (terrain_ref.GroundSwingRef) and the tick's solve read the plane and the normal that the
+    previous tick's update left; after the plant's step terrain_ref.tick_step runs on the float32
+    pos_feet the controller saw and on ~swing, and (n, d) go, rounded to float32, to the swing leg
+    (under ``terrain_ground`` as terrain_ref.ground_plane, MPCQP_TERRAIN_GROUND; without it the
+    fitted (n, d) itself) and to words 9..11 of the robot records.  The run then also holds plane
+    [T,B,4] float64 (the record's n, d) and fitted [T,B]; with a plane or a stage it holds swing
+    [T,B,4] (the stage latches ~swing) and foothold [T,B,4,3], every leg's swing memory after the
+    tick.  With both left out nothing of this is touched."""
     import os
     import sys
     pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pympc-quadruped_amd")
@@ -341,17 +376,30 @@ def closed_loop(commands, ticks, robot="aliengo", gait="trot10", horizon=10, ibm
     period, off, dur = int(grec[0]), tuple(int(x) for x in grec[1:5]), tuple(int(x) for x in grec[5:9])
     gaits = np.tile(grec, (B, 1))
     sw = SWING_PRESETS[robot]
-    swing = swing_ref.SwingRef(B, dt_control=par.dt_control, gravity=par.gravity, swing_height=sw["swing_height"],
-                               kp=sw["kp"], kd=sw["kd"])
+    swing_kw = dict(dt_control=par.dt_control, gravity=par.gravity, swing_height=sw["swing_height"], kp=sw["kp"],
+                    kd=sw["kd"])
+    if terrain is None:
+        swing = swing_ref.SwingRef(B, **swing_kw)
+    else:
+        import terrain_ref
+        swing = terrain_ref.GroundSwingRef(B, **swing_kw)
+        ter_state = np.zeros((B, terrain_ref.STRIDE))
     planners = [PlannerOracle(horizon, height, dt_control=par.dt_control, gravity=par.gravity) for _ in range(B)]
     vb = np.stack([cmd, np.zeros(B), np.zeros(B)], 1)
     yr = np.zeros(B)
     root, dofs = stand_pose(B, geom, par, height=height if heights is None else np.asarray(heights, np.float32))
-    rec = reset(root, dofs, geom, par)
+    if plane is not None:
+        pl = np.asarray(plane, np.float32).reshape(B, 4).astype(np.float64)
+        # the pose is turned onto the plane the caller gives (tilt and azimuth read back from its
+        # float32 words: the pose is off it by their rounding, which the first landing takes up)
+        root, _ = tilt_pose(root, np.arctan2(np.hypot(pl[:, 0], pl[:, 1]), pl[:, 2]), np.arctan2(-pl[:, 1], -pl[:, 0]), par)
+        plane = pl.astype(np.float32)
+    rec = reset(root, dofs, geom, par, plane)
     rec0 = rec.copy()
     u0 = np.zeros((B, 12), np.float32)
     f4 = np.float32
-    log = dict(height=[], roll=[], pitch=[], x=[], solve_ok=[], finite=[], touch=[], tau=[])
+    log = dict(height=[], roll=[], pitch=[], x=[], solve_ok=[], finite=[], touch=[], tau=[], plane=[], fitted=[],
+               swing=[], foothold=[])
     ok = np.ones(B, bool)
     for t in range(ticks):
         quat = np.concatenate([root[:, 6:7], root[:, 3:6]], 1)
@@ -377,8 +425,19 @@ def closed_loop(commands, ticks, robot="aliengo", gait="trot10", horizon=10, ibm
         out = swing.step(np.full(B, t), ibm, gaits, pos, vel, swing_ref.quat2matrix_f32(quat), vb, yr, k32["thighs"],
                          k32["pos_feet"], k32["foot_pos_base"], k32["foot_vel_base"], k32["jac"], u0)
         tau = out["tau"]
-        res = plant_step(rec, tau, rrec, geom, par)
+        res = plant_step(rec, tau, rrec, geom, par, plane)
         root, dofs = res["root"], res["dofs"]
+        if terrain is not None:
+            ter_state, ter_ok = terrain_ref.tick_step(ter_state, k32["pos_feet"], ~out["swing"], terrain)
+            n, d = ter_state[:, terrain_ref.N], ter_state[:, terrain_ref.D]
+            swing.set_ground(terrain_ref.ground_plane(n, d, swing.touchdown_z) if terrain_ground
+                             else np.concatenate([n, d[:, None]], 1).astype(f4))
+            rrec[:, 9:12] = n.astype(f4)
+            log["plane"].append(ter_state[:, 13:17].copy())
+            log["fitted"].append((ter_state[:, terrain_ref.FITTED] != 0.0) & ter_ok)
+        if terrain is not None or plane is not None:
+            log["swing"].append(out["swing"].copy())
+            log["foothold"].append(swing.mem[:, :, swing_ref.FINAL].copy())
         roll, pitch = euler_zyx(rec[:, QUAT:QUAT + 4])
         log["height"].append(rec[:, 2].copy())
         log["roll"].append(roll)

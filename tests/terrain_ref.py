@@ -14,7 +14,8 @@ import swing_ref
 STRIDE = 20                                          # MPCQP_TERRAIN_STRIDE
 HIST, INIT, N, D, FITTED = slice(0, 12), 12, slice(13, 16), 16, 17
 STATUS_OK, STATUS_NONFINITE = 0, 4
-SWING_STATE, ROOT_STATES = 1, 2                      # MPCQP_TERRAIN_SWING_STATE, MPCQP_TERRAIN_ROOT_STATES
+SWING_STATE, ROOT_STATES, GROUND = 1, 2, 4            # MPCQP_TERRAIN_SWING_STATE, _ROOT_STATES, _GROUND
+TOUCHDOWN_Z = -0.0255                                # mpcqp_set_swing's default
 DEFAULTS = dict(contact_threshold=0.5, flat_tol=1e-3, cos_max_tilt=0.5, blend=1.0)
 TROT10 = np.array([10, 0, 5, 5, 0, 5, 5, 5, 5], np.int32)   # Gait.TROTTING10 (gait.py:17)
 
@@ -87,16 +88,26 @@ def tick_step(state, feet, contact, constants=None):
     return np.where(ok[:, None], new, st), ok
 
 
-def terrain_step(state, inp, constants=None):
+def ground_plane(n, d, touchdown_z=TOUCHDOWN_Z):
+    """The plane handed to the swing leg under MPCQP_TERRAIN_GROUND, [B,4] float32: the swing leg
+    places a foothold at touchdown_z + ground(x, y), so (n, d - n_z touchdown_z) puts it on
+    n . p = d, the plane through the latched foot centres."""
+    n, d = np.asarray(n, np.float64), np.asarray(d, np.float64)
+    return np.concatenate([n, (d - n[:, 2] * touchdown_z)[:, None]], axis=1).astype(np.float32)
+
+
+def terrain_step(state, inp, constants=None, ground=False, touchdown_z=TOUCHDOWN_Z):
     """A launch: inp has pos_feet, contact or swing_state, optionally quat (or root_states)
     and robot [B,16].  Returns (state, outputs): normal, plane, normal_base (with a
-    quaternion), status, robot (with a robot) as the kernel stores them."""
+    quaternion), status, robot (with a robot) as the kernel stores them.  ``ground``:
+    MPCQP_TERRAIN_GROUND, plane is ground_plane(n, d, touchdown_z)."""
     swing_rule = "swing_state" in inp
     cont = contact_decision(inp["swing_state"] if swing_rule else inp["contact"], constants, swing_rule)
     new, ok = tick_step(state, inp["pos_feet"], cont, constants)
     src = np.where(ok[:, None], new, as_was(state))
     out = dict(normal=src[:, N].astype(np.float32),
-               plane=np.concatenate([src[:, N], src[:, D:D + 1]], axis=1).astype(np.float32),
+               plane=ground_plane(src[:, N], src[:, D], touchdown_z) if ground
+               else np.concatenate([src[:, N], src[:, D:D + 1]], axis=1).astype(np.float32),
                status=np.where(ok, STATUS_OK, STATUS_NONFINITE).astype(np.int32))
     quat = None
     if inp.get("root_states") is not None:
@@ -113,7 +124,7 @@ def terrain_step(state, inp, constants=None):
     return new, out
 
 
-def run(traj, constants=None, swing_rule=True, state0=None):
+def run(traj, constants=None, swing_rule=True, state0=None, **kw):
     """make_trajectory's ticks through terrain_step from zero records: states [T,B,20] and
     the outputs stacked [T,B,...]."""
     B = traj[0]["pos_feet"].shape[0]
@@ -122,7 +133,7 @@ def run(traj, constants=None, swing_rule=True, state0=None):
     for t in traj:
         inp = dict(pos_feet=t["pos_feet"], quat=t["quat"])
         inp["swing_state" if swing_rule else "contact"] = t["swing_state"] if swing_rule else t["contact"]
-        st, o = terrain_step(st, inp, constants)
+        st, o = terrain_step(st, inp, constants, **kw)
         states.append(st)
         outs.append(o)
     return np.stack(states), {k: np.stack([o[k] for o in outs]) for k in outs[0]}
@@ -206,6 +217,13 @@ class GroundSwingRef(swing_ref.SwingRef):
             self.on = np.isfinite(g).all(axis=1) & (g[:, 2] > 0)
         self.ground = np.where(self.on[:, None], g, [0.0, 0.0, 1.0, 0.0])
 
+    def set_ground(self, ground):
+        """Another set of planes [B,4], as a caller's write into the buffer of mpcqp_set_ground."""
+        g = np.asarray(ground, np.float32).astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            self.on = np.isfinite(g).all(axis=1) & (g[:, 2] > 0)
+        self.ground = np.where(self.on[:, None], g, [0.0, 0.0, 1.0, 0.0])
+
     def height(self, p):
         """ground(x, y) of p [B,4,3] -> [B,4]; 0 without a plane."""
         g = self.ground[:, None, :]
@@ -261,3 +279,129 @@ class GroundSwingRef(swing_ref.SwingRef):
         tau = np.where(sw, tau_sw, tau_st).reshape(-1, 12).astype(np.float32)
         cur = np.where(swing, t_swing - remaining, -np.inf)
         return dict(tau=tau, swing=swing, swing_state=value, pos_target=pt, vel_target=vt, cur=cur)
+
+
+# ---- the closed loop with the terrain stage: plant -> controller -> terrain -> controller on the
+# CPU oracles (plant_ref.closed_loop with plane= and terrain=), recorded in
+# tests/golden/terrain_loop.npz by tests/golden/make_golden_terrain_loop.py
+
+LOOP = dict(robot="aliengo", gait="trot10", horizon=10, ibm=20)
+LOOP_TICKS = 800
+# (name, tilt in rad, the compass direction in which the ground climbs in degrees (0: ahead of
+# the robot), forward command in m/s, start).  start "ground": the stand pose with its feet on
+# the plane, the premise of the stage (a latched stance foot is a sample of the ground); "drop":
+# plant_ref.closed_loop's own start at the preset's height, the feet 0.023 m in the air.
+LOOP_SCENARIOS = (("level, standing", 0.0, 0, 0.0, "ground"), ("level, 0.5 m/s", 0.0, 0, 0.5, "ground"),
+                  ("uphill 0.1 rad, standing", 0.1, 0, 0.0, "ground"), ("uphill 0.1 rad, 0.3 m/s", 0.1, 0, 0.3, "ground"),
+                  ("cross-slope 0.1 rad, 0.3 m/s", 0.1, 90, 0.3, "ground"),
+                  ("downhill 0.1 rad, 0.3 m/s", 0.1, 180, 0.3, "ground"),
+                  ("uphill 0.2 rad, standing", 0.2, 0, 0.0, "ground"), ("uphill 0.2 rad, 0.3 m/s", 0.2, 0, 0.3, "ground"),
+                  ("level, 0.5 m/s, dropped", 0.0, 0, 0.5, "drop"), ("uphill 0.1 rad, 0.3 m/s, dropped", 0.1, 0, 0.3, "drop"))
+LOOP_LEVEL = (0, 1)                                          # the scenarios of the level-ground comparison
+LOOP_FIGURES = ("height", "tilt", "speed", "normal", "foothold", "touchdown", "fitted")
+
+
+def loop_planes(scenarios=LOOP_SCENARIOS, ground_z=TOUCHDOWN_Z):
+    """[B,4] float32, the plant's ground per scenario: (n, ground_z), n = (-sin tilt cos az,
+    -sin tilt sin az, cos tilt) (plant_ref.tilt_pose)."""
+    tilt = np.array([s[1] for s in scenarios], np.float64)
+    az = np.deg2rad(np.array([s[2] for s in scenarios], np.float64))
+    n = np.stack([-np.sin(tilt) * np.cos(az), -np.sin(tilt) * np.sin(az), np.cos(tilt)], axis=1)
+    n[np.abs(n) < 1e-16] = 0.0                               # sin(pi), cos(pi / 2)
+    return np.concatenate([n, np.full((len(tilt), 1), ground_z)], axis=1).astype(np.float32)
+
+
+def loop_heights(scenarios=LOOP_SCENARIOS, robot="aliengo", preset=0.38):
+    """[B] float32: the base height of the level stand pose each scenario starts from, before
+    plant_ref.tilt_pose turns it onto the plane."""
+    import plant_ref
+    params = plant_ref._presets()
+    geom = params.pack_leg_geometry(params.LEG_GEOMETRY[robot], 1)
+    on_ground = plant_ref.stand_pose(1, geom, plant_ref.Params())[0][0, 2]
+    return np.array([on_ground if s[4] == "ground" else preset for s in scenarios], np.float32)
+
+
+def closed_loop_terrain(scenarios=LOOP_SCENARIOS, stage=True, ground=True, ticks=LOOP_TICKS, constants=None):
+    """plant_ref.closed_loop over the scenarios, one robot each: with the terrain stage (``ground``:
+    under MPCQP_TERRAIN_GROUND) or without.  Returns the run with ``planes``."""
+    import plant_ref
+    planes = loop_planes(scenarios)
+    run = plant_ref.closed_loop([s[3] for s in scenarios], ticks, plane=planes, terrain_ground=ground,
+                                terrain=dict(constants or {}) if stage else None,
+                                heights=loop_heights(scenarios, LOOP["robot"]), **LOOP)
+    run["planes"] = planes
+    return run
+
+
+def clean_ticks(swing, touch):
+    """swing [T,B,4] bool, touch [T,B,4] (the plant's, after the tick's step) -> [T,B] bool: every
+    point of the history after the update of tick t was latched while its foot stood on the
+    ground.  The stage latches by the schedule (~swing); a foot whose stance has begun by the
+    schedule and that is still coming down -- it lands three ticks late in this loop -- is latched
+    in the air, millimetres up, until it lands, and so is a foot that the seed tick takes in
+    mid-air.  Whether it stood is the plant's touch after the step of tick t - 1, the pose that
+    the pos_feet of tick t show (for tick 0 the pose it starts in: touch after reset is not
+    logged, so a foot counts as standing where it touches after the first step and is in stance)."""
+    touch = np.asarray(touch) != 0
+    stance = ~np.asarray(swing, bool)
+    before = np.concatenate([touch[:1], touch[:-1]], axis=0)
+    ok = np.zeros(stance.shape, bool)
+    ok[0] = before[0] & stance[0]
+    for t in range(1, len(ok)):
+        ok[t] = np.where(stance[t], before[t], ok[t - 1])
+    return ok.all(axis=2)
+
+
+def foothold_offsets(foothold, planes):
+    """The vertical distance of every foothold [T,B,4,3] from the plant's plane [B,4]."""
+    pl = np.asarray(planes, np.float32).astype(np.float64)[None, :, None, :]
+    f = np.asarray(foothold, np.float64)
+    return f[..., 2] - (pl[..., 3] - pl[..., 0] * f[..., 0] - pl[..., 1] * f[..., 1]) / pl[..., 2]
+
+
+def loop_figures(run, height=0.38, last=500):
+    """Per robot [B]:
+      height, tilt, speed   plant_ref.summary's three: worst |height - desired|, worst roll /
+                            pitch, mean forward speed along x over the last ticks
+      start                 the first clean tick (clean_ticks): every foot latched on the ground
+      clean                 the share of clean ticks from there on
+      foothold              the worst vertical distance from the plant's plane of a swing leg's
+                            foothold over the ticks t > start whose plane, the one the update of
+                            tick t - 1 left, was clean
+      touchdown             the same over the last tick of every swing that begins after start:
+                            the foothold the leg comes down on
+      foothold_any          the same over every swing tick after start, clean or not
+    and with the stage
+      normal                the largest difference (max norm) of the fitted normal, rounded to
+                            float32, from the plane's float32 normal over the clean ticks
+      normal_any            the same over every tick from start on
+      fitted                the share of ticks with an accepted fit."""
+    import plant_ref
+    h, tilt, speed = plant_ref.summary(run, height=height, last=last)
+    swing = np.asarray(run["swing"], bool)
+    T, B = swing.shape[:2]
+    clean = clean_ticks(swing, run["touch"])
+    assert clean.any(axis=0).all()
+    start = np.argmax(clean, axis=0)
+    t = np.arange(T)[:, None]
+    after = t > start[None, :]
+    prev_clean = np.concatenate([np.zeros((1, B), bool), clean[:-1]], axis=0)
+    off = np.abs(foothold_offsets(run["foothold"], run["planes"]))
+    worst = lambda mask: np.where(mask, off, 0.0).max(axis=(0, 2))
+    begins = swing & ~np.concatenate([np.zeros((1, B, 4), bool), swing[:-1]], axis=0)
+    begun_after = np.zeros_like(swing)                        # in a swing that began after start
+    for k in range(1, T):
+        begun_after[k] = swing[k] & np.where(begins[k], after[k][:, None], begun_after[k - 1])
+    ends = begun_after & ~np.concatenate([swing[1:], np.ones((1, B, 4), bool)], axis=0)
+    assert ends.any(axis=(0, 2)).all()
+    fig = dict(height=h, tilt=tilt, speed=speed, start=start,
+               clean=np.array([clean[start[b]:, b].mean() for b in range(B)]),
+               foothold=worst(swing & (after & prev_clean)[..., None]), touchdown=worst(ends),
+               foothold_any=worst(swing & after[..., None]))
+    if "plane" in run:
+        n32 = run["plane"][:, :, :3].astype(np.float32).astype(np.float64)
+        err = np.abs(n32 - run["planes"][None, :, :3].astype(np.float64)).max(axis=2)
+        fig["normal"] = np.where(clean, err, 0.0).max(axis=0)
+        fig["normal_any"] = np.where(t >= start[None, :], err, 0.0).max(axis=0)
+        fig["fitted"] = run["fitted"].mean(axis=0)
+    return fig

@@ -231,7 +231,7 @@ def test_argument_errors():
             "pos_feet", "contact", "quat", "state", "robot", "normal", "plane", "normal_base", "status")), None)
 
     err = lambda: lib.mpcqp_last_error(ctx).decode()
-    refused = [(dict(flags=4), "flags"), (dict(flags=-1), "flags"), (dict(batch=-1), "batch"),
+    refused = [(dict(flags=8), "flags"), (dict(flags=-1), "flags"), (dict(batch=-1), "batch"),
                (dict(pos_feet=None), "null"), (dict(contact=None), "null"), (dict(state=None), "null"),
                (dict(state=odd), "aligned"), (dict(quat=None), "normal_base")]
     for kw, word in refused:

@@ -25,6 +25,7 @@ import re
 import numpy as np
 import pytest
 
+import terrain_edge_checks as edge
 import terrain_ref as tr
 from helpers import _declared, host_build
 
@@ -40,11 +41,11 @@ SHIM = r'''
 #include "mpcqp_terrain_robot.h"
 #include "mpcqp_swing_leg.h"
 // a launch of mpcqp_terrain_kernel, robot after robot; c: contact_threshold, flat_tol,
-// cos_max_tilt, blend
+// cos_max_tilt, blend, touchdown_z
 extern "C" void launch(const double* c, int flags, int B, const float* pos_feet, const float* contact,
                        const float* quat, double* st, float* robot, float* normal, float* plane,
                        float* normal_base, int32_t* status) {
-  const TerParams tp{c[0], c[1], c[2], c[3], flags};
+  const TerParams tp{c[0], c[1], c[2], c[3], flags, c[4]};
   for (int b = 0; b < B; ++b)
     ter_robot(tp, (size_t)b, pos_feet, contact, quat, st, robot, normal, plane, normal_base, status);
 }
@@ -52,6 +53,7 @@ extern "C" void eig(const double* S, double* l, double* v) { ter_eig(S, l, v); }
 extern "C" int stride(void) { return TER_STRIDE; }
 extern "C" int flag_swing(void) { return TER_SWING_STATE; }
 extern "C" int flag_root(void) { return TER_ROOT_STATES; }
+extern "C" int flag_ground(void) { return TER_GROUND; }
 // in: t_swing, t_stance, dt, finished, pos[3], vel[3], R[9], vbody[3], yaw_rate, thigh[3], foot[3],
 // gravity, vel_gain, touchdown_z, swing_height (33 doubles); which: 0 swing_leg_step, 1 _ground
 extern "C" void leg_step(int which, double* mem, const double* in, const double* ground, double* pb, double* vb) {
@@ -83,6 +85,7 @@ def test_constants_match_binding(robot):
     assert define("MPCQP_TERRAIN_STRIDE") == _lib.TERRAIN_STRIDE == tr.STRIDE == robot.stride() == 20
     assert define("MPCQP_TERRAIN_SWING_STATE") == _lib.TERRAIN_SWING_STATE == tr.SWING_STATE == robot.flag_swing()
     assert define("MPCQP_TERRAIN_ROOT_STATES") == _lib.TERRAIN_ROOT_STATES == tr.ROOT_STATES == robot.flag_root()
+    assert define("MPCQP_TERRAIN_GROUND") == _lib.TERRAIN_GROUND == tr.GROUND == robot.flag_ground() == 4
     assert tr.STATUS_NONFINITE == _lib.STATUS_NONFINITE
 
 
@@ -117,13 +120,13 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def host_launch(lib, state, inp, constants=None, pad=2, skip=()):
+def host_launch(lib, state, inp, constants=None, pad=2, skip=(), ground=False, touchdown_z=tr.TOUCHDOWN_Z):
     """A launch on the host, on `state` [B + pad, STRIDE] in place; the outputs come back with
-    their `pad` sentinel rows.  `skip`: outputs passed as NULL."""
+    their `pad` sentinel rows.  `skip`: outputs passed as NULL.  `ground`: MPCQP_TERRAIN_GROUND."""
     B = state.shape[0] - pad
     c = dict(tr.DEFAULTS, **(constants or {}))
-    cv = np.array([c[k] for k in ("contact_threshold", "flat_tol", "cos_max_tilt", "blend")])
-    flags = 0
+    cv = np.array([c[k] for k in ("contact_threshold", "flat_tol", "cos_max_tilt", "blend")] + [touchdown_z])
+    flags = tr.GROUND if ground else 0
     if "swing_state" in inp:
         flags |= tr.SWING_STATE
         contact = np.ascontiguousarray(inp["swing_state"], np.float32)
@@ -452,6 +455,104 @@ def test_reference_recorded_run(robot):
         assert (st[:B, tr.FITTED] == 1).all()
     print(f"\nours against eigh's column {ours:.2e}; the reference's row against it {differs:.2e}")
     assert ours < 1e-12 and differs > 1e-3
+
+
+# ---- the edges, shared with tests/test_gpu_terrain_edges.py (tests/terrain_edge_checks.py)
+
+@pytest.fixture(scope="module")
+def launch(robot):
+    def run(state, inp, constants=None, ground=False):
+        B = len(state)
+        st = np.vstack([np.asarray(state, np.float64), np.full((2, tr.STRIDE), float(SENTINEL))])
+        out = host_launch(robot, st, inp, constants, ground=ground)
+        assert (st[B:] == SENTINEL).all() and all((v[B:] == SENTINEL).all() for k, v in out.items() if k != "robot")
+        return st[:B].copy(), {k: v[:B] for k, v in out.items()}
+    return run
+
+
+@pytest.fixture(scope="module")
+def gpu_traj():
+    return tr.make_trajectory(**tr.GPU_TRAJECTORY)
+
+
+def test_cases_are_what_they_claim(gpu_traj):
+    """Every edge case on terrain_ref alone: the decision it is meant to take, and its distance
+    from the threshold -- a factor 2 and more for a spread and for the length of a blend, 0.02 rad
+    for a tilt (n_z 1.7e-2 off cos_max_tilt, 1e5 float32 roundings), or an exact zero."""
+    flat, cmt = tr.DEFAULTS["flat_tol"], tr.DEFAULTS["cos_max_tilt"]
+    rows = {name: (fitted, spread, nz, l2) for name, fitted, spread, nz, l2 in edge.describe_held()}
+    for name in edge.HELD:
+        assert not rows[name][0], name
+    for name in edge.ACCEPTED:
+        assert rows[name][0], name
+    assert rows["coincident"][3] == 0.0 and rows["collinear"][1] < 1e-12 and rows["collinear"][3] > 0.1
+    assert abs(rows["spread flat_tol / 2"][1] / (flat / 2) - 1) < 1e-3 and abs(rows["spread 2 flat_tol"][1] / (2 * flat) - 1) < 1e-3
+    for name in ("spread flat_tol / 2", "spread 2 flat_tol"):
+        assert rows[name][2] > cmt + 0.1                       # the tilt does not decide these
+    assert abs(rows["tilt 0.02 rad past the limit"][2] - np.cos(edge.ACOS_HALF + 0.02)) < 1e-6
+    assert abs(rows["tilt 0.02 rad inside the limit"][2] - np.cos(edge.ACOS_HALF - 0.02)) < 1e-6
+    for name in ("tilt 0.02 rad past the limit", "tilt 0.02 rad inside the limit"):
+        assert abs(rows[name][2] - cmt) > 1.7e-2 and rows[name][1] > 0.1
+    assert abs(rows["vertical plane"][2]) < 1e-12 and rows["vertical plane"][1] > 0.1
+    # the seeded normals at blend = 0.5: the blend's length is exactly 0, and 1.5 / 1.45
+    recs, feet = edge.seeded_n_records()
+    _, _, nf = tr.fit(feet.astype(np.float64)[None])
+    assert nf[0].tolist() == [0.0, 0.0, 1.0]
+    ln = np.linalg.norm(0.5 * recs[:, tr.N] + 0.5 * nf, axis=1)
+    assert ln[0] == 0.0 and ln[1] == 1.5 and 1.4 < ln[2] < 1.5
+    # the thin footprints: accepted, spread a factor 2 and more over flat_tol
+    thin = edge.thin_feet()
+    sp = tr.spread(thin.astype(np.float64))
+    st, ok = tr.tick_step(np.zeros((len(thin), tr.STRIDE)), thin, np.ones((len(thin), 4), bool))
+    assert ok.all() and (st[:, tr.FITTED] == 1).all() and sp.min() >= 2 * flat * (1 - 1e-4) and sp.max() <= 0.05 * (1 + 1e-4)
+    # the bad records: refused but for the cold one
+    rows_, rec = edge.bad_records()
+    moved = np.tile(edge.rectangle(0.2, 0.13, 0.25, -1.0, (1.5, -1.75, 0.525)), (len(rows_), 1, 1))
+    with np.errstate(invalid="ignore"):
+        _, ok = tr.tick_step(rows_, moved, np.ones((len(rows_), 4), bool))
+    assert ok.tolist() == [False] * 18 + [True] and len(rows_) == 19
+    # far from the origin: the larger coordinate is 7e3 .. 1e4 and 7e4 .. 1e5 m, where float32
+    # positions are 2^-11 or 2^-10 (5e-4, 1e-3 m) and 2^-7 (8e-3 m) apart
+    far = edge.far_feet()
+    gap = np.round(np.log2(np.spacing(np.abs(far).max(axis=(1, 2))))).astype(int)
+    assert set(gap[0::2]) <= {-11, -10} and set(gap[1::2]) == {-7}
+    # the blend trajectory: spread 0.05 and more, asserted by the generator itself
+    assert len(gpu_traj) >= 10 and gpu_traj[0]["pos_feet"].shape[0] >= edge.B_EDGE
+
+
+def test_edge_held_fits(launch):
+    print(f"\nheld fits: d and accepted n against the restatement {edge.check_held_fits(launch):.2e} of the bound")
+
+
+def test_edge_blend_and_seeded_normals(launch, gpu_traj):
+    print(f"\nblend 0.25 / 0.5 over 10 ticks: {edge.check_blend(launch, gpu_traj):.2e} (bound {edge.N_BOUND:.1e})")
+    edge.check_seeded_normals(launch)
+
+
+def test_edge_exact_structure_and_scaling(launch):
+    w = edge.check_exact_structure(launch)
+    rows = edge.check_scaling(launch)
+    print(f"\nexact structure {w:.2e} of the bound; {rows} scaled rows bitwise")
+
+
+def test_edge_thin_footprints(launch):
+    err = edge.check_thin_footprints(launch)
+    print("\nthin footprints, spread: error (bound)  " + "  ".join(
+        f"{s}: {e:.2e} ({edge.N_BOUND * max(1, 0.05 / s):.1e})" for s, e in err.items()))
+
+
+def test_edge_odd_inputs_and_bad_records(launch):
+    edge.check_odd_inputs(launch)
+    print(f"\nrefused records: {edge.check_bad_records(launch)}")
+
+
+def test_edge_far_from_the_origin(launch):
+    worst, fitted = edge.check_far_from_the_origin(launch)
+    print(f"\n1e4 / 1e5 m from the origin: {worst:.2e} (bound {edge.N_BOUND:.1e}); share fitted per tick {fitted}")
+
+
+def test_edge_ground_flag(launch, gpu_traj):
+    print(f"\nground flag: plane word against d - n_z touchdown_z {edge.check_ground_flag(launch, gpu_traj):.2e}")
 
 
 # ---- the swing leg on the plane
